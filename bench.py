@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py - BASELINE.json's metric on BASELINE.json's configs, through the C-ABI.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--extra-configs 3,4,5,6] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--dump-outputs DIR] [--full [--extra-configs 3,4,5,6] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's results if `--dump-outputs` is given and
+prints the headline.  Everything else below - the `configs` records, the same-tapes leg, the replayed stream check, the CPU
+baselines, the measured HBM peak, the details file - runs only with `--full`.
 
 `--gpus N` with N > 1 starts its own N ranks (one process per GPU under torch.distributed.run, 127.0.0.1, a free port); under a
 launcher that already set WORLD_SIZE (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N`) it
@@ -56,6 +60,8 @@ PROFILE_DIRS = [os.path.join(ROOT, "profiles", name) for name in ("r06", "r05", 
 # full-rate and H half-rate instructions issues at most (F + H) / (F / 78.6 + H / 39.3) T lane-operations/s; F and H come from
 # the code object's own assembly (scripts/opcode_mix.py -> profiles/r03/opcode_mix.json).
 VALU_FULL_RATE_PEAK, VALU_HALF_RATE_PEAK = 78.6e12, 39.3e12  # 256 CUs x 4 SIMDs x 32 (16) lanes x 2.4 GHz
+SETTLE_SECONDS = 2.0  # a plain run's untimed calls ahead of its warm-up (main: what the `configs` records do for a --full run)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def _profile_json(name):
@@ -83,6 +89,12 @@ def parse_args():
     parser.add_argument("--steps", type=int, default=200)
     parser.add_argument("--warmup", type=int, default=20)
     parser.add_argument("--config", type=int, default=2, help="BASELINE.json config index of the headline (2 = the metric's config)")
+    parser.add_argument("--full", action="store_true",
+                        help="also measure and check everything beyond the headline: the `configs` records, the same-tapes leg, the replayed "
+                             "stream check, the CPU baselines, the measured HBM peak and the details file (off: the headline alone)")
+    parser.add_argument("--dump-outputs", default=None, metavar="DIR",
+                        help="after the timed steps, write the matrix the last timed step returned as DIR/distances.npy (scores.npy for "
+                             "NW / SW) in float64; above 64 MB, a fixed seeded sample of whole rows, their indices in DIR/<name>_rows.npy")
     parser.add_argument("--generator", default="mt19937_64", choices=["numpy", "mt19937_64"],
                         help="where configs 1-4 come from: std::mt19937_64, the generator SURVEY.md section 8(d) names "
                              "(csrc/workloads/workloads_mt19937.cpp spells the mapping out; reproducible from C++), or numpy's "
@@ -122,7 +134,12 @@ def parse_args():
     parser.add_argument("--c-node-leg", default=None, metavar="CONFIG:DEVICE,DEVICE,...",
                         help="internal: ONE strong-scaled record through the single-process C node driver, printed as a JSON line (the N > 1 "
                              "run calls itself with this in a child process: first contact with real peers must not cost the headline line)")
-    return parser.parse_args()
+    args = parser.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        parser.error("--steps must be at least 1 and --warmup at least 0")
+    if args.extra_configs is not None and args.extra_configs.strip().lower() not in ("", "none") and not args.full:
+        parser.error("--extra-configs names records of a --full run")
+    return args
 
 
 def resolve_generator(wanted):
@@ -178,6 +195,20 @@ def measured_hbm_peak(where):
         best = seconds if best is None else min(best, seconds)
     del source, target
     return round(2.0 * size / best / 1e9, 1)
+
+
+def dump_outputs(directory, name, results):
+    """`--dump-outputs`: the results matrix of the last timed step as `directory/<name>.npy` in float64 (every cell is an integer of
+    far fewer than 53 bits), so that two builds can be compared output for output on the same seeded batches.  A matrix above
+    DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of whole rows, written with their indices as `<name>_rows.npy`."""
+    os.makedirs(directory, exist_ok=True)
+    rows, columns = results.shape
+    if rows * columns * 8 > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - rows * 8) // (columns * 8))
+        picked = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        np.save(os.path.join(directory, f"{name}_rows.npy"), picked.astype(np.float64))
+        results = results[results.new_tensor(picked)]
+    np.save(os.path.join(directory, f"{name}.npy"), results.cpu().numpy().astype(np.float64))
 
 
 # ---- engines and entry points per workload kind -------------------------------------------------------------------------
@@ -727,8 +758,11 @@ def free_port():
 
 def launch_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves (one process per GPU under
-    `torch.distributed.run`, rendezvous on 127.0.0.1 and a free port, the same argv) and become them.  A box with fewer than N
+    `torch.distributed.run`, rendezvous on 127.0.0.1 and a free port, the same argv) in a child process and exit with its code
+    (this process has opened the device to count GPUs: it must not replace itself with another program).  A box with fewer than N
     devices gets a parseable line and a non-zero exit, not a traceback ("missing" #2)."""
+    import subprocess
+
     import torch
 
     visible = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -738,7 +772,7 @@ def launch_ranks(args):
     command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, command)
+    raise SystemExit(subprocess.run(command).returncode)
 
 
 def c_node_leg_in_a_child(config, devices, args):
@@ -771,7 +805,7 @@ def main():
         print(json.dumps(record if record is not None else {"config": int(config), "entry_point": "szs_rocm_node_scores_u32tape", "error": "this build has no node driver"}), flush=True)
         return
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        launch_ranks(args)  # does not return
+        launch_ranks(args)  # exits with the ranks' code
     clock = {"started": time.perf_counter()}
     # The application's choice, made before HIP initialises: twelve hardware queues, so that the per-width launches of a
     # mixed-length batch (configs 5 / 5u: up to eight streams) each get their own.  The library itself never writes the
@@ -842,8 +876,10 @@ def main():
     # ---- the other configs run BEFORE the headline's warm-up: a run of W = 5 short warm-up steps on a GPU that has idled
     # through the set-up is timed on its clock ramp (round 1: 64.4 TCUPS with 20 steps against 67.9 with 200); after seconds
     # of NW / SW scoring the clocks are where a busy GPU keeps them.  The headline itself is unchanged: W untimed steps, then
-    # exactly K timed ones.  (The single-process C driver of N > 1 runs last, while the other ranks wait.)
-    if args.extra_configs is None:
+    # exactly K timed ones.  (The single-process C driver of N > 1 runs last, while the other ranks wait.)  Only with --full.
+    if not args.full:
+        extras = []
+    elif args.extra_configs is None:
         extras = [9, 3, 4, 5, 6, 7, 8, 10, 12] if not distributed else [2, 4, 5]  # N > 1: the metric's own batch and the two 8-GPU configs, STRONG-scaled
     else:
         extras = [] if args.extra_configs.strip().lower() in ("", "none") else [int(x) for x in args.extra_configs.split(",")]
@@ -861,7 +897,7 @@ def main():
         except Exception as problem:  # an extra record must never cost the headline line
             records.append({"config": config, "error": repr(problem)})
 
-    if not distributed and args.extra_configs is None:
+    if args.full and not distributed and args.extra_configs is None:
         try:
             records.append(measure_fingerprints(scope, local_rank, args, fence))
         except Exception as problem:
@@ -880,6 +916,15 @@ def main():
         other_candidates = fresh_tape(args.generator, 4243 + 10 * rank, len(load.candidates), 96, 160).to_device(local_rank)
         other_step = make_step(engine, scope, load, other, other_candidates, results, local_rank)
         steps_of.append(other_step)
+    if not args.full:
+        # A plain run has no `configs` records to keep the GPU busy before the headline: seconds of untimed calls of the timed stream
+        # take their place, so that its steps are timed where a busy GPU keeps its clocks, as in a --full run
+        fence()
+        settle_started, index = time.perf_counter(), 0
+        while time.perf_counter() - settle_started < SETTLE_SECONDS:
+            steps_of[index % len(steps_of)]()
+            index += 1
+    if args.config == 2:
         for _ in range(max(2, args.warmup // 2)):
             step()
         # (at least 400 calls, ~76 ms: the same-tapes figure is an average over them, and the power management has then settled on this
@@ -893,16 +938,19 @@ def main():
         fence()
         same_elapsed = time.perf_counter() - same_started
         profile = engine.last_call_profile()
-        # the same tapes again and again: the plan of the previous call is re-used behind a guard, no planner kernel
-        same_tapes = {"ms_per_step": round(same_elapsed / calls * 1e3, 4), "value": round(profile.cells * calls / same_elapsed / 1e9, 1),
-                      "unit": "GCUPS", "calls": calls, "planner_mode": int(profile.planner)}
+        # the same tapes again and again: the plan of the previous call is re-used behind a guard, no planner kernel (reported with
+        # --full; a plain run keeps these calls as warm-up)
+        if args.full:
+            same_tapes = {"ms_per_step": round(same_elapsed / calls * 1e3, 4), "value": round(profile.cells * calls / same_elapsed / 1e9, 1),
+                          "unit": "GCUPS", "calls": calls, "planner_mode": int(profile.planner)}
 
     for index in range(args.warmup):
         steps_of[index % len(steps_of)]()
-    cells_of_step = []
+    cells_of_step, profiles_of_step = [], []
     for one in steps_of:  # cells per call of each batch (untimed; also leaves every plan shape warm)
         one()
-        cells_of_step.append(float(engine.last_call_profile().cells))
+        profiles_of_step.append(engine.last_call_profile())
+        cells_of_step.append(float(profiles_of_step[-1].cells))
     kernel_ms, planners, timed_cells = [], set(), 0.0
     fence()
     started = time.perf_counter()
@@ -917,24 +965,26 @@ def main():
         slowest = torch.tensor([elapsed], dtype=torch.float64, device=where)
         dist.all_reduce(slowest, op=dist.ReduceOp.MAX)
         elapsed = float(slowest)
-    # ---- every batch of the timed stream is CHECKED, outside the timed region (bench/similarities.cuh:410-423 checks every batch it
-    # times): (a) the stream is replayed - the same calls in the same order - with the matrix summed on the device after every call
-    # and compared with that batch's own sum; (b) below, on rank 0, each batch's whole matrix is compared cell for cell with the
-    # reference's engines (`cpu_baseline.checked`, `stream_check`)
-    sums_of_batches, matrices_of_batches = [], []
-    for one in steps_of:
-        one()
-        sums_of_batches.append(int(results.sum().item()))
-        if rank == 0 and not args.no_cpu_baseline and len(steps_of) > 1:
-            matrices_of_batches.append(results.cpu().numpy().copy())
-    replayed, replay_mismatches = min(args.steps, 200), 0
-    for index in range(replayed):
-        steps_of[index % len(steps_of)]()
-        replay_mismatches += int(results.sum().item()) != sums_of_batches[index % len(steps_of)]
-    assert replay_mismatches == 0, f"{replay_mismatches} of {replayed} replayed calls of the timed stream wrote another matrix"
-    step()  # untimed: the headline batch's own matrix is what the checksum and the CPU baseline look at
-
-    profile = engine.last_call_profile()
+    profile = profiles_of_step[0]  # the headline batch's call: its cells, bytes, launches and cell width
+    if args.dump_outputs and rank == 0:  # `results` still holds what the last timed step wrote (rank 0's own query rows)
+        dump_outputs(args.dump_outputs, "distances" if load.kind.startswith("levenshtein") else "scores", results)
+    if args.full:
+        # ---- every batch of the timed stream is CHECKED, outside the timed region (bench/similarities.cuh:410-423 checks every batch it
+        # times): (a) the stream is replayed - the same calls in the same order - with the matrix summed on the device after every call
+        # and compared with that batch's own sum; (b) below, on rank 0, each batch's whole matrix is compared cell for cell with the
+        # reference's engines (`cpu_baseline.checked`, `stream_check`)
+        sums_of_batches, matrices_of_batches = [], []
+        for one in steps_of:
+            one()
+            sums_of_batches.append(int(results.sum().item()))
+            if rank == 0 and not args.no_cpu_baseline and len(steps_of) > 1:
+                matrices_of_batches.append(results.cpu().numpy().copy())
+        replayed, replay_mismatches = min(args.steps, 200), 0
+        for index in range(replayed):
+            steps_of[index % len(steps_of)]()
+            replay_mismatches += int(results.sum().item()) != sums_of_batches[index % len(steps_of)]
+        assert replay_mismatches == 0, f"{replay_mismatches} of {replayed} replayed calls of the timed stream wrote another matrix"
+        step()  # untimed: the headline batch's own matrix is what the checksum and the CPU baseline look at
 
     device_ids = torch.zeros(world, dtype=torch.float64, device=where)
     device_ids[rank] = float(torch.cuda.current_device() + 1)
@@ -942,11 +992,13 @@ def main():
         dist.all_reduce(device_ids)
     devices_in_use = len({int(v) for v in device_ids.tolist()})
     cells_per_rank = torch.tensor([timed_cells], dtype=torch.float64, device=where)  # over the K timed steps
-    checksum = results.sum().reshape(1).to(torch.float64)
     if distributed:
         dist.all_reduce(cells_per_rank)
-        dist.all_reduce(checksum)
     total_cells = float(cells_per_rank)
+    if args.full:
+        checksum = results.sum().reshape(1).to(torch.float64)
+        if distributed:
+            dist.all_reduce(checksum)
 
     if distributed and extras:
         fence()
@@ -965,7 +1017,6 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         value = total_cells / elapsed / 1e9
         kernel = float(np.mean(kernel_ms)) * 1e-3  # seconds per launch group, hipEvent pair on the library's stream
-        gpu_matrix = results.cpu().numpy()
         valu_table, _ = _profile_json("valu_peak.json")
         pure = (valu_table or {}).get("myers_pure_W4_Tcells")
         lengths = load.queries.lengths().astype(np.int64)
@@ -974,12 +1025,13 @@ def main():
         # scoring launch (planner mode 4), the same tapes again run the plain launch behind the guard (mode 3)
         leg = "fresh" if planners == {4} else "same_tapes" if planners == {3} else None
         line_roofline = roofline(args.config, profile, kernel, args.hbm_traffic_bytes, leg=leg)
-        try:  # device-to-device copy of 1 GiB on this box, read + write bytes over the best of five (torch, HIP events)
-            line_roofline["peak_measured"] = measured_hbm_peak(where)
-            line_roofline["frac_of_measured_peak"] = round(line_roofline["achieved"] / line_roofline["peak_measured"], 6)
-        except Exception as problem:
-            line_roofline["peak_measured"] = None
-            line_roofline["peak_measured_error"] = repr(problem)[:80]
+        if args.full:
+            try:  # device-to-device copy of 1 GiB on this box, read + write bytes over the best of five (torch, HIP events)
+                line_roofline["peak_measured"] = measured_hbm_peak(where)
+                line_roofline["frac_of_measured_peak"] = round(line_roofline["achieved"] / line_roofline["peak_measured"], 6)
+            except Exception as problem:
+                line_roofline["peak_measured"] = None
+                line_roofline["peak_measured_error"] = repr(problem)[:80]
         if load.kind == "levenshtein" and pure:
             # the ceiling of the kernel's own column update on register-resident masks, measured: scripts/valu_peak.hip
             # `myers_pure_W4_Tcells`; cells counted at full bit-vector width (phantom rows included) on both sides
@@ -1006,18 +1058,19 @@ def main():
             "roofline": line_roofline,
             "host_overhead_ms_per_step": round(ms_per_step - kernel * 1e3, 4),
             "planner": "+".join({0: "host", 1: "device", 2: "device, speculated", 3: "re-used", 4: "inside the scoring launch", 5: "none (tiny tokens)"}[mode] for mode in sorted(planners)),
-            "results_checksum": float(checksum),
             # the three figures the reference's own bench prints per engine (bench/similarities.cuh:344-366: bytes passed, operations =
             # cells, inputs processed, and the device-measured "Kernel" line :303-308)
             "reference_style": {"throughput_gb_s": round(float(load.queries.lengths().sum() * columns + load.candidates.lengths().sum() * rows) * world / (elapsed / args.steps) / 1e9, 1),
                                 "efficiency_gops_s": round(value, 1), "pairs_per_second": round(rows * columns * world / (elapsed / args.steps), 0),
                                 "kernel_gcups": round(float(profile.cells) / kernel / 1e9, 1)},
         }
+        if args.full:
+            line["results_checksum"] = float(checksum)
         if same_tapes is not None:
             line["config"]["same_tapes_gcups"] = same_tapes["value"]
             line["same_tapes"] = same_tapes
-        if not args.no_cpu_baseline:  # rank 0, whatever N: the host cores are this box's
-            line["cpu_baseline"] = cpu_baseline(load, gpu_matrix, args.cpu_seconds, cell_bits=profile.cell_bits, verify_seconds=args.verify_seconds)
+        if args.full and not args.no_cpu_baseline:  # rank 0, whatever N: the host cores are this box's
+            line["cpu_baseline"] = cpu_baseline(load, results.cpu().numpy(), args.cpu_seconds, cell_bits=profile.cell_bits, verify_seconds=args.verify_seconds)
             line["stream_check"] = {"replayed_calls": replayed, "checksum_mismatches": replay_mismatches, "batches": len(steps_of)}
             if len(matrices_of_batches) > 1:  # the OTHER batch of the alternating stream, cell for cell as well
                 other_load = type("other", (), {"queries": other_step.keepalive[2], "candidates": other_step.keepalive[3], "kind": load.kind,
@@ -1032,7 +1085,7 @@ def main():
         clock["done"] = time.perf_counter()
         line["run_seconds"] = {"total": round(clock["done"] - clock["started"], 1), "gpu_legs": round(clock["gpu_done"] - clock["started"], 1),
                                "cpu_baselines": round(clock["done"] - clock["gpu_done"], 1)}
-        emit(line, records, args.details)
+        emit(line, records, args.details if args.full else None)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()

@@ -37,7 +37,7 @@ for step in "$@"; do
                     echo "--- node_probe $args (SZS_ROCM_QUEUE=1)"; SZS_ROCM_QUEUE=1 timeout 300 tests/native/bin/node_probe_asan $args 2>&1 | grep -v "^    #" | tail -6; done
                   echo "--- fingerprints_probe"; timeout 300 tests/native/bin/fingerprints_probe_asan 64 50 100 5000 1 2>&1 | tail -4; } > "$OUT/asan.log" 2>&1
                 grep -c "ERROR: AddressSanitizer\|runtime error" "$OUT/asan.log"; tail -40 "$OUT/asan.log";;
-    bench)      timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 3000 "$OUT/bench.json"; tail -3 "$OUT/bench.err";;
+    bench)      timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 3000 "$OUT/bench.json"; tail -3 "$OUT/bench.err";;
     configs)    timeout 600 python scripts/measure_configs.py --configs 2,3,4,5 > "$OUT/configs.jsonl" 2>&1; cat "$OUT/configs.jsonl";;
     timeline5)  timeout 300 bash scripts/gpu_timeline.sh 5 8 > "$OUT/timeline_cfg5_eighth.txt" 2>&1; tail -30 "$OUT/timeline_cfg5_eighth.txt";;
     timeline6)  timeout 300 bash scripts/gpu_timeline.sh 6 8 > "$OUT/timeline_cfg6_eighth.txt" 2>&1; tail -30 "$OUT/timeline_cfg6_eighth.txt";;

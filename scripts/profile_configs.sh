@@ -1,6 +1,6 @@
 #!/bin/bash
 # profile_configs.sh TAG [CONFIG ...] - per BASELINE.json config, the SAME command bench.py's `configs` records time
-# (`bench.py --config N --extra-configs none`), under
+# (`bench.py --full --config N --extra-configs none`), under
 #   1. rocprofv3 --kernel-trace --stats            -> gpurun_out/TAG/cfgN/stats/*kernel_stats.csv   (average durations)
 #   2. PMC passes, each in its own run, never mixed with trace domains other than --kernel-trace
 #                                                  -> gpurun_out/TAG/cfgN/pmc_*/
@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for N in "${CONFIGS[@]}"; do
     case $N in 2) STEPS=(--steps 50 --warmup 5);; 4) STEPS=(--steps 2 --warmup 1);; *) STEPS=(--steps 5 --warmup 1);; esac
-    ARGS=(--config "$N" --extra-configs none --no-cpu-baseline "${STEPS[@]}")
+    ARGS=(--full --config "$N" --extra-configs none --no-cpu-baseline "${STEPS[@]}")
     [ "$N" = 11 ] && ARGS=(--fingerprints-only --extra-seconds 0.05) # `szs_fingerprints_u32tape` alone: cfg11:fingerprint_segments_kernel
     D=$OUT/cfg$N; mkdir -p "$D"
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o stats -- python "$ROOT/bench.py" "${ARGS[@]}" > "$D/bench.json" 2> "$D/stats.log" \

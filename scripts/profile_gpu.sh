@@ -11,7 +11,7 @@
 # HBM traffic unit corrections (MI355X_MICROARCH.md, HBM section) are applied by pmc_summary.py, not here.
 set -u
 TAG=${1:-run}; shift || true
-ARGS=("$@")
+ARGS=(--full "$@")
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"

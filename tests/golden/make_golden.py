@@ -3,7 +3,7 @@
 
 Run in the build container only (needs /root/reference):
 
-    make -C oracle ref && python tests/golden/make_golden.py
+    make -C oracle ref && python tests/golden/make_golden.py            (--fuzz-only: reference_fuzz.npz alone)
 
 It drives oracle/_ref/libszs_ref.so - the reference's own serial engines (`levenshtein_serial_t`,
 `needleman_wunsch_serial_t`, `smith_waterman_serial_t` and the affine siblings; include/stringzillas/similarities/
@@ -183,6 +183,46 @@ def main_utf8():
     print(f"wrote {path}: {len(cases)} cases, {os.path.getsize(path) / 1024:.0f} KiB")
 
 
+def main_fuzz():
+    """tests/golden/reference_fuzz.npz: every answer the reference's engines give to the seeded fuzz of tests/test_oracle.py
+    (`test_live_fuzz_*`), call by call - run with the live engines, recorded, and replayed by those tests where oracle/_ref is
+    not built.  The inputs are the tests' own: they are not stored, only what the reference returned to them."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle
+
+    assert ob.reference_available(), "needs oracle/_ref (make -C oracle ref)"
+    stored, live_engine = {}, test_oracle._reference_engine
+
+    class Recorder:
+        def __init__(self, key, engine):
+            self.key, self.engine, self.calls = key, engine, 0
+
+        def __getattr__(self, name):
+            def record(*args, **kwargs):
+                result = getattr(self.engine, name)(*args, **kwargs)
+                parts = result if isinstance(result, tuple) else (result,)
+                for index, part in enumerate(parts):
+                    stored[f"{self.key}/{self.calls}/{index}"] = np.asarray(part)
+                stored[f"{self.key}/{self.calls}/parts"] = np.asarray(len(parts))
+                self.calls += 1
+                stored[f"{self.key}/calls"] = np.asarray(self.calls)
+                return result
+            return record
+
+    test_oracle._reference_engine = lambda key, live: Recorder(key, live_engine(key, live))
+    oracle = ob.oracle()
+    for tier in (0, 2):
+        test_oracle.test_live_fuzz_against_reference(oracle, tier)
+        test_oracle.test_live_fuzz_utf8_against_reference(oracle, tier)
+    test_oracle.test_live_fuzz_fingerprints_against_reference(oracle)
+    np.savez_compressed(os.path.join(HERE, "reference_fuzz.npz"), **stored)
+    print("wrote reference_fuzz.npz:", len(stored), "arrays")
+
+
+if __name__ == "__main__" and "--fuzz-only" in sys.argv:
+    main_fuzz()
+    sys.exit(0)
+
 if __name__ == "__main__" and "--fingerprints-only" in sys.argv:
     main_fingerprints()
     sys.exit(0)
@@ -192,3 +232,4 @@ if __name__ == "__main__":
         main()
         main_fingerprints()
     main_utf8()
+    main_fuzz()

@@ -8,6 +8,8 @@ import subprocess
 import sys
 from contextlib import redirect_stdout
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -179,3 +181,51 @@ def test_committed_bench_outputs_pass_the_audit():
         records = [entry["configs_record"] for entry in printed if "configs_record" in entry]
         assert bench.audit(line, records) == [], path
         assert line.get("audit", []) == [], path
+
+
+def test_dumped_outputs_are_float64_and_sampled_above_the_limit(tmp_path, monkeypatch):
+    """`--dump-outputs`: the whole matrix in float64 when it fits the limit; above it, the same seeded rows every time, with their
+    indices beside them."""
+    import numpy as np
+    import torch
+
+    matrix = torch.arange(64 * 48, dtype=torch.int64).reshape(64, 48)
+    bench.dump_outputs(str(tmp_path / "whole"), "distances", matrix)
+    whole = np.load(tmp_path / "whole" / "distances.npy")
+    assert whole.dtype == np.float64 and np.array_equal(whole, matrix.numpy()) and not (tmp_path / "whole" / "distances_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 48 * 8)
+    for attempt in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / attempt), "scores", matrix)
+    rows = np.load(tmp_path / "a" / "scores_rows.npy").astype(np.int64)
+    sample = np.load(tmp_path / "a" / "scores.npy")
+    assert sample.nbytes + rows.nbytes <= bench.DUMP_LIMIT_BYTES and 0 < len(rows) < 64 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(sample, matrix.numpy()[rows]) and np.array_equal(sample, np.load(tmp_path / "b" / "scores.npy"))
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line alone (no `configs` records, no CPU baseline, no
+    details file), exactly K timed steps, and with --dump-outputs the matrix of the last timed step - here the third of the
+    alternating stream, config 2's own batch - equal to the same call made directly."""
+    import numpy as np
+
+    import stringzilla_amd as szs
+    from stringzilla_amd import workloads
+
+    details = tmp_path / "details.json"
+    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs",
+               str(tmp_path / "out"), "--details", str(details)]
+    done = subprocess.run(command, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert done.returncode == 0, done.stdout[-3000:] + done.stderr[-3000:]
+    printed = [json.loads(text) for text in done.stdout.splitlines() if text.startswith("{")]
+    assert len(printed) == 1 and not details.exists()
+    line = printed[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert "cpu_baseline" not in line and "same_tapes" not in line and "configs_gcups" not in line and line["audit"] == []
+    dumped = np.load(tmp_path / "out" / "distances.npy")
+    load = workloads.config(2, generator="mt19937_64")
+    gpu = szs.DeviceScope(gpu_device=0)
+    expected = szs.LevenshteinDistances(capabilities=gpu)(load.queries, load.candidates, device=gpu)
+    assert dumped.dtype == np.float64 and dumped.shape == (1024, 1024) and np.array_equal(dumped, expected.astype(np.float64))

@@ -30,7 +30,7 @@ def test_ranks_on_one_device(ranks, launcher, tmp_path):
     from stringzilla_amd import matrices, workloads
 
     scale = 1 / 8
-    options = ["--gpus", str(ranks), "--steps", "5", "--warmup", "2", "--backend", "gloo", "--same-device", "--extra-scale", str(scale),
+    options = ["--gpus", str(ranks), "--full", "--steps", "5", "--warmup", "2", "--backend", "gloo", "--same-device", "--extra-scale", str(scale),
                "--extra-seconds", "0.2", "--cpu-seconds", "1", "--extra-cpu-seconds", "0.5",
                "--details", str(tmp_path / "bench_configs.json")]  # not gpurun_out/bench_configs.json: that is the real run's
     if launcher == "torchrun":
@@ -90,7 +90,7 @@ def test_two_ranks_on_two_devices_over_rccl(tmp_path):
     from stringzilla_amd import workloads
 
     scale = 1 / 8
-    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--backend", "nccl",
+    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "5", "--warmup", "2", "--backend", "nccl",
                "--extra-scale", str(scale), "--extra-seconds", "0.2", "--cpu-seconds", "1", "--extra-cpu-seconds", "0.5", "--extra-configs", "2,5",
                "--details", str(tmp_path / "bench_configs.json")]
     environment = {key: value for key, value in os.environ.items() if key not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
@@ -119,7 +119,7 @@ def test_the_distributed_path_over_rccl_with_a_world_of_one(tmp_path):
     from stringzilla_amd import matrices, workloads
 
     scale = 1 / 8
-    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-distributed", "--backend", "nccl", "--steps", "5", "--warmup", "2",
+    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-distributed", "--backend", "nccl", "--steps", "5", "--warmup", "2",
                "--extra-scale", str(scale), "--extra-seconds", "0.2", "--cpu-seconds", "1", "--extra-cpu-seconds", "0.5",
                "--details", str(tmp_path / "bench_configs.json")]
     environment = {key: value for key, value in os.environ.items() if key not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
