@@ -13,6 +13,7 @@
  *    without a GPU (tests/test_host_logic.py).
  *  - szs_rocm_node_*            : one cross-product over the N GPUs of a host, in C (csrc/host/node.c).
  *  - szs_rocm_tuning_set        : the tuning / testing knobs.
+ *  - szs_rocm_top_k*            : the k best candidates of every query, without the queries x candidates matrix (csrc/host/top_k.c).
  */
 #ifndef STRINGZILLAS_ROCM_H_
 #define STRINGZILLAS_ROCM_H_
@@ -66,6 +67,33 @@ SZ_API_RUNTIME sz_status_t szs_rocm_shard_rows(sz_size_t const *row_weights, sz_
  */
 SZ_API_RUNTIME sz_status_t szs_rocm_shard_triangle(sz_size_t const *lengths, sz_size_t rows, sz_size_t shards, sz_size_t *band_first,
                                                    sz_u64_t *band_weights);
+
+/**
+ *  The k best candidates of every query, in one call, without materialising the queries x candidates matrix: the call is scored
+ *  tile by tile (ordinary engine calls into device scratch) and every tile is folded into per-query lists on the device.
+ *
+ *  `engine`: a Levenshtein, Levenshtein UTF-8, Needleman-Wunsch or Smith-Waterman engine; any other handle is refused and nothing
+ *  is written.  Row q receives `indices[q * row_stride + r]` and, when `scores` is not NULL, `scores[q * row_stride + r]` for
+ *  r < k: 8-byte cells of the engine's own type (`sz_size_t` distances, `sz_ssize_t` scores).  Cells [k, row_stride) are left
+ *  untouched.  Distances rank ascending, NW / SW scores descending; equal scores go to the LOWER candidate index.
+ *
+ *  `candidates` NULL: SELF-SEARCH - the queries against themselves, each query's own index excluded (duplicates at other indices
+ *  count).  Unlike the matrix calls, where NULL means the symmetric matrix with its diagonal.
+ *
+ *  A row with fewer than k candidates (C < k, or C - 1 < k in self-search) is completed with index SZ_SIZE_MAX and score 0.
+ *  1 <= k <= 1024 and row_stride >= k, else sz_unexpected_dimensions_k.  Zero queries: success, nothing written; zero candidates:
+ *  every row is completed that way.  Candidate counts beyond 2^32 are fine.  Inputs and outputs may live in host, pinned, unified
+ *  or device memory, as for the matrix calls.  Synchronous, also when it fails.  The `top_k_tile` knob caps the candidates of a tile.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_top_k(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                          sz_sequence_t const *candidates, sz_size_t k, sz_size_t *indices, void *scores,
+                                          sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                  sz_sequence_u32tape_t const *candidates, sz_size_t k, sz_size_t *indices,
+                                                  void *scores, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                  sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices,
+                                                  void *scores, sz_size_t row_stride, char const **error_message);
 
 /**
  *  Runs the host planner on bare length arrays.  Outputs (all optional):
@@ -211,6 +239,7 @@ SZ_API_RUNTIME sz_status_t szs_rocm_node_scores_u64tape(szs_rocm_node_engine_t e
  *  call inside its own scoring launch), "tiny" (0: never | 1: every unit-cost byte call of strings up to 255 bytes of which
  *  few are beyond 16 - the tiny-token launch of hip/myers_tiny.hip | 2: the same, and blocks full of longer strings are scored there
  *  too, slowly, instead of refused (testing); automatic: batches of tiny tokens on both sides),
+ *  "top_k_tile" (n: the most candidates per scored tile of a top-k call),
  *  "queues" (see below), "roctx" (1: the host phases of every call - plan, decide, enqueue, wait - as roctx ranges for a
  *  `rocprofv3 --marker-trace` timeline; the marker library is looked up at run time, never linked),
  *  "cpu_requests" (strict | gpu: serve capability

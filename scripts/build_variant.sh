@@ -9,7 +9,7 @@ OUT=$ROOT/stringzilla_amd/lib_variants/$NAME
 make -s -C "$ROOT/stringzilla_amd/csrc" -j8
 mkdir -p "$OUT"
 rm -rf "$OUT/obj"; cp -r "$ROOT/stringzilla_amd/lib/obj" "$OUT/obj"
-if [ $# -gt 0 ]; then for object in "$@"; do rm -f "$OUT/obj/$object.o"; done; else rm -f "$OUT"/obj/*.o; fi
+if [ $# -gt 0 ]; then for object in "$@"; do rm -f "$OUT/obj/$object.o" "$OUT/obj/hip/$object.o"; done; else rm -f "$OUT"/obj/*.o "$OUT"/obj/hip/*.o; fi
 find "$OUT/obj" -name "*.o" -exec touch {} +
 make -s -C "$ROOT/stringzilla_amd/csrc" -j8 OUT="../lib_variants/$NAME" EXTRA="$FLAGS"
 ls -la "$OUT/libstringzillas_rocm_shared.so"

@@ -296,6 +296,63 @@ class _Engine:
             return out
         return results.cpu().numpy().view(self._dtype)
 
+    def top_k(self, queries, candidates=None, k=None, device: Optional[DeviceScope] = None, out=None):
+        """The `k` best candidates of every query (`szs_rocm_top_k_*`) without the full matrix: returns `(indices, scores)`, a
+        `uint64` and an engine-dtype `(rows, k)` NumPy matrix, or fills `out=(indices, scores)` (NumPy arrays or torch tensors of
+        8-byte cells, one row stride; `scores` may be None).  Distances rank ascending, NW / SW scores descending, ties go to the
+        lower candidate index.  `candidates` None: self-search, each query's own index excluded.  A row with fewer than `k`
+        candidates ends in index 2**64 - 1 and score 0."""
+        import torch
+
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError(f"k must be an integer within [1, 1024], got {k!r}")
+        k = int(k)
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        queries = _as_strs(queries)
+        candidates = None if candidates is None else _as_strs(candidates)
+        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
+            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        rows = len(queries)
+
+        def cells_of(matrix, name):  # -> (pointer, row stride in cells)
+            if matrix is None:
+                return None, None
+            if isinstance(matrix, np.ndarray):
+                shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
+                pointer = matrix.ctypes.data
+            else:
+                shape, itemsize, strides, pointer = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr()
+                if matrix.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
+                    torch.cuda.current_stream(matrix.device).synchronize()
+            if shape != (rows, k) or itemsize != 8 or (k > 1 and strides[1] != 1):
+                raise ValueError(f"`out` {name} must be a (rows, k) matrix of 8-byte cells with contiguous rows")
+            return pointer, strides[0] if rows > 1 else k
+
+        if out is None:
+            both = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+            indices_pointer, scores_pointer, stride = both[0].data_ptr(), both[1].data_ptr(), k
+        else:
+            indices_pointer, stride = cells_of(out[0], "indices")
+            scores_pointer, scores_stride = cells_of(out[1], "scores")
+            if indices_pointer is None:
+                raise ValueError("`out` indices must not be None")
+            if scores_pointer is not None and scores_stride != stride:
+                raise ValueError("`out` indices and scores must share one row stride")
+
+        error = ctypes.c_char_p()
+        call = lib.szs_rocm_top_k_u64tape if queries.wide_offsets else lib.szs_rocm_top_k_u32tape
+        q_tape = queries._tape(gpu_device)
+        c_tape = None if candidates is None else candidates._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape), k,
+                      indices_pointer, scores_pointer, stride, ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        host = both[:, :rows].cpu().numpy()
+        return host[0].view(np.uint64), host[1].view(self._dtype)
+
     def __del__(self):
         handle = getattr(self, "handle", None)
         if handle and self._free is not None:

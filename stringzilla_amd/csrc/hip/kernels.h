@@ -228,6 +228,28 @@ int szs_hip_utf8_narrow(szs_tape_t const *queries, szs_tape_t const *candidates,
  */
 int szs_hip_mirror_lower(uint64_t *matrix, uint32_t side, uint64_t row_stride, void *stream);
 
+/**
+ *  Top-k selection over scored tiles (hip/top_k.hip; host/top_k.c).  Every query row keeps a RUNNING LIST of
+ *  width = szs_hip_top_k_width(k) (the power of two >= k) exact (key, candidate index) pairs, ascending: 2 * width words, keys then
+ *  indices, pairs (~0, ~0) where nothing is yet; a list buffer filled with 0xFF bytes is an empty list.  The key is the cell for
+ *  distances and the order-reversing image of the signed score when `descending`; ties go to the lower candidate index.
+ *
+ *  szs_hip_top_k_scan folds the tile `cells[r * cells_stride + c]` (r < rows, c < columns; its column c is candidate
+ *  first_column + c) into the running lists of rows 0 ... rows - 1.  `self_first_row` != ~0: row r is query self_first_row + r of a
+ *  self-search and its own candidate index is skipped.  `segments` workgroups share a row (a second launch merges their partial
+ *  lists); `partials` holds rows * segments lists when segments > 1.  Tiles of a row must arrive in ascending column order.
+ *  szs_hip_top_k_emit writes the first k pairs of each list as indices[r * stride + i] and scores[r * stride + i] (scores may be
+ *  NULL); an empty pair becomes index ~0 and score 0.
+ */
+#define SZS_TOP_K_MOST 1024u
+size_t szs_hip_top_k_width(uint32_t k);
+size_t szs_hip_top_k_scan_lds_bytes(uint32_t k);
+int szs_hip_top_k_scan(uint64_t const *cells, uint64_t cells_stride, uint32_t rows, uint32_t columns, uint64_t first_column,
+                       uint64_t self_first_row, uint64_t *lists, uint64_t *partials, uint32_t segments, uint32_t k, int descending,
+                       void *stream);
+int szs_hip_top_k_emit(uint64_t const *lists, uint32_t rows, uint32_t k, uint64_t *indices, uint64_t *scores, uint64_t stride,
+                       int descending, void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {
@@ -260,6 +282,7 @@ enum {
                                sorters never publish - every waiting workgroup runs out of polls, the call is planned the ordinary way */
     szs_knob_tiny_k,        /* -1 automatic (tiny tokens on both sides) | 0 never | 1 every unit-cost byte call of strings up to 255 bytes, few
                                of them beyond 16: the tiny-token launch of hip/myers_tiny.hip | 2 (testing): dense batches are scored there too */
+    szs_knob_top_k_tile_k,  /* -1 automatic | n: the most candidates per scored tile of a top-k call (host/top_k.c) */
     szs_knob_count_k
 };
 int szs_tuning_get(int knob);

@@ -273,6 +273,9 @@ static void release_device_state(szs_engine_s *engine) {
     szs_buffer_release(&engine->pinned_summary);
     szs_buffer_release(&engine->pinned_squares);
     szs_buffer_release(&engine->device_fused);
+    szs_buffer_release(&engine->device_top_k_scratch);
+    szs_buffer_release(&engine->device_top_k_lists);
+    szs_buffer_release(&engine->device_top_k_out);
     engine->tiny_valid = 0, engine->tiny_runes_valid = 0, engine->narrow_zeroed = NULL;
     engine->fused_zeroed = NULL;
     if (engine->events_device >= 0) {
@@ -287,6 +290,16 @@ static void release_device_state(szs_engine_s *engine) {
     }
     engine->model_uploaded_device = -1;
     if (engine->remembered) engine->remembered->valid = 0;
+}
+
+void szs_engine_follow_device(szs_engine_s *engine, int device) {
+    if (engine->device == device) return; /* scratch follows the device of the call */
+    if (engine->device >= 0) {
+        (void)hipSetDevice(engine->device);
+        release_device_state(engine);
+        (void)hipSetDevice(device);
+    }
+    engine->device = device;
 }
 
 void szs_engine_release(szs_engine_s *engine) {
@@ -1217,14 +1230,7 @@ sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input
     if (!results) return szs_report(sz_status_unknown_k, error_message, "Results must not be null");
     if (results_row_stride < candidates_count) return szs_report(sz_unexpected_dimensions_k, error_message, NULL);
 
-    if (engine->device != device) { /* scratch follows the device of the call */
-        if (engine->device >= 0) {
-            (void)hipSetDevice(engine->device);
-            release_device_state(engine);
-            (void)hipSetDevice(device);
-        }
-        engine->device = device;
-    }
+    szs_engine_follow_device(engine, device);
     if (engine->events_device != device) {
         hipError_t error = hipEventCreate(&engine->event_start);
         if (error == hipSuccess) error = hipEventCreate(&engine->event_stop);

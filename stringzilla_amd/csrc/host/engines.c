@@ -262,3 +262,30 @@ sz_status_t szs_rocm_last_call_profile(void *handle, szs_rocm_call_profile_t *pr
     *profile = engine->last_profile;
     return sz_success_k;
 }
+
+/* ---- top-k (host/top_k.c) --------------------------------------------------------------------------------------------- */
+
+#define SZS_TOP_K_BODY(MAKE_INPUT)                                                                                     \
+    if (k < 1 || k > SZS_TOP_K_MOST || row_stride < k || !queries)                                                     \
+        return szs_engine_top_k((szs_engine_s *)engine, (szs_scope_s *)device, NULL, NULL, k, indices, scores,         \
+                                row_stride, error_message);                                                            \
+    szs_input_t const query_input = MAKE_INPUT(queries);                                                               \
+    szs_input_t candidate_input;                                                                                       \
+    if (candidates) candidate_input = MAKE_INPUT(candidates);                                                          \
+    return szs_engine_top_k((szs_engine_s *)engine, (szs_scope_s *)device, &query_input,                               \
+                            candidates ? &candidate_input : NULL, k, indices, scores, row_stride, error_message);
+
+sz_status_t szs_rocm_top_k(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, sz_sequence_t const *candidates,
+                           sz_size_t k, sz_size_t *indices, void *scores, sz_size_t row_stride, char const **error_message) {
+    SZS_TOP_K_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_top_k_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                   sz_sequence_u32tape_t const *candidates, sz_size_t k, sz_size_t *indices, void *scores,
+                                   sz_size_t row_stride, char const **error_message) {
+    SZS_TOP_K_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                   sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices, void *scores,
+                                   sz_size_t row_stride, char const **error_message) {
+    SZS_TOP_K_BODY(input_from_u64tape)
+}

@@ -144,6 +144,11 @@ typedef struct szs_engine_s {
     uint32_t plan_sequence;        /* echoed by the planner: tells this call's summary from a stale one */
     struct szs_decision_t *remembered; /* the launch shape of the previous device-planned call (speculation), or NULL */
 
+    /* top-k calls (host/top_k.c) */
+    szs_buffer_t device_top_k_scratch; /* device: the scored tile */
+    szs_buffer_t device_top_k_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
+    szs_buffer_t device_top_k_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
+
     szs_rocm_call_profile_t last_profile;
 } szs_engine_s;
 
@@ -315,5 +320,13 @@ void szs_plan_orient(unsigned bit_parallel_limit, int bit_parallel_chain, int af
 sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries,
                              szs_input_t const *candidates /* NULL: symmetric */, void *results,
                              size_t results_row_stride, char const **error_message);
+/** Releases the engine's device buffers when `device` is not the one they live on (dispatch.c). */
+void szs_engine_follow_device(szs_engine_s *engine, int device);
+
+/* ---- top-k (top_k.c) ---------------------------------------------------------------------------------------------------- */
+
+/** `candidates` NULL: self-search (each query against all queries but itself). */
+sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                             size_t k, size_t *indices, void *scores, size_t row_stride, char const **error_message);
 
 #endif /* SZS_INTERNAL_H_ */
