@@ -343,6 +343,9 @@ typedef struct szs_plan_summary_t {
      * [0] the shortest, [SZS_PLAN_RANK_SAMPLES] the longest; every string of a lower rank is no longer than the sample */
     uint32_t rank_lengths[2][SZS_PLAN_RANK_SAMPLES + 1];
 } szs_plan_summary_t;
+/* SZS_PLAN_TIMESTAMPS builds (a measuring aid): the planner leaves 8 timestamps of its phases this many bytes behind the start of
+ * the summary (host/dispatch_internal.h: szs_pinned_words_t checks that they fall behind it) */
+#define SZS_PLAN_TIMESTAMPS_AT 448u
 
 /**
  *  Plans one call on the device: reads the offsets of both tapes (`candidates` NULL: symmetric), writes for each side the

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(plan_threads_k) void plan_kernel(szs_plan_side_t qu
     int const mine = symmetric ? 0 : (int)blockIdx.x; // the side this workgroup plans: 0 the caller's queries, 1 its candidates
     szs_plan_side_t const &side = mine ? candidates : queries;
 #ifdef SZS_PLAN_TIMESTAMPS // measuring aid (build variant): 100 MHz timestamps of the phases, behind the summary, for the trace
-    unsigned long long *const stamps = reinterpret_cast<unsigned long long *>(summary) + 56;
+    unsigned long long *const stamps = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(summary) + SZS_PLAN_TIMESTAMPS_AT);
 #define SZS_PLAN_STAMP(K) do { if (tid == 0 && mine == 0) stamps[K] = wall_clock64(); } while (0)
 #else
 #define SZS_PLAN_STAMP(K) do {} while (0)

@@ -276,7 +276,7 @@ static void release_device_state(szs_engine_s *engine) {
     szs_buffer_release(&engine->device_top_k_scratch);
     szs_buffer_release(&engine->device_top_k_lists);
     szs_buffer_release(&engine->device_top_k_out);
-    engine->tiny_valid = 0, engine->tiny_runes_valid = 0, engine->narrow_zeroed = NULL;
+    szs_tiny_forget(&engine->tiny[0]), szs_tiny_forget(&engine->tiny[1]), engine->narrow_zeroed = NULL;
     engine->fused_zeroed = NULL;
     if (engine->events_device >= 0) {
         (void)hipEventDestroy(engine->event_start);
@@ -785,7 +785,7 @@ hipError_t szs_call_enqueue(szs_engine_s *engine, szs_decision_t const *d, int d
             trace = (uint64_t *)engine->device_queue_trace.pointer;
         /* a query that fits no table of the kernel (the plan's job to prevent) raises this flag in pinned memory: szs_engine_cross
          * looks after the call's wait and scores the batch with the per-width launches instead */
-        uint32_t *const unfit = (uint32_t *)((char *)engine->pinned_summary.pointer + 960);
+        uint32_t *const unfit = (uint32_t *)&szs_pinned_words(engine)->queue_unfit;
         engine->queue_unfit_sequence = ++engine->plan_sequence;
         launch_error = szs_hip_levenshtein_myers_queue(&d->queue, query_refs, candidate_refs, (uint64_t *)device_results, device_stride, d->layout,
                                                        (uint32_t *)engine->device_queue.pointer, engine->queue_tickets, &taken, trace,
@@ -865,11 +865,11 @@ sz_status_t szs_call_finish(szs_call_t *call, szs_decision_t const *d, hipError_
     szs_engine_s *engine = call->engine;
     hipStream_t const stream = call->stream;
     int const chained = d->tier == SZS_TIER_SYSTOLIC || d->tier == SZS_TIER_MYERS_CHAIN;
-    uint64_t *const stall_flag = (uint64_t *)engine->pinned_summary.pointer + 64; /* behind the planner's summary */
+    uint64_t volatile *const stall_flag = &szs_pinned_words(engine)->stall_flag;
     *stall_flag = 0;
     if (error == hipSuccess && status == sz_success_k) error = hipEventRecord(engine->event_stop, stream);
     if (error == hipSuccess && status == sz_success_k && chained)
-        error = hipMemcpyAsync(stall_flag, (char *)engine->device_systolic.pointer + 8, sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+        error = hipMemcpyAsync((void *)stall_flag, (char *)engine->device_systolic.pointer + 8, sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
     if (error == hipSuccess && status == sz_success_k && !call->direct) /* one strided copy back into the caller's host matrix
                                                                            (reference: cuMemcpy2DAsync, cuda.cuh:2205-2215) */
         error = hipMemcpy2DAsync(call->results, call->results_row_stride * sizeof(uint64_t), call->device_results,
@@ -919,7 +919,7 @@ sz_status_t szs_call_finish(szs_call_t *call, szs_decision_t const *d, hipError_
     szs_call_phase(call, 5);
 #ifdef SZS_PLAN_TIMESTAMPS
     if (call->trace) {
-        unsigned long long const *stamps = (unsigned long long const *)engine->pinned_summary.pointer + 56;
+        unsigned long long const volatile *stamps = szs_pinned_words(engine)->plan_timestamps;
         fprintf(stderr, "planner phases (10 ns ticks):");
         for (int k = 1; k < 8; ++k) fprintf(stderr, " %lld", (long long)(stamps[k] - stamps[k - 1]));
         fprintf(stderr, "\n");
@@ -1033,13 +1033,12 @@ static int device_plannable(szs_engine_s const *engine, szs_input_t const *input
     return szs_classify_pointer(input->offsets).device_accessible && szs_classify_pointer(input->data).device_accessible;
 }
 
-/** 256 bytes of device memory per engine, zeroed when allocated and never again: the two `ready` words of the launch that plans
- *  itself (dwords 0 and 32; kernels.h: szs_fused_plan_t) and the verdict words of the two-workgroup planner (dwords 48 ... 55). */
+/** The engine's szs_device_words_t, zeroed when allocated and after a failed call (szs_call_finish), never by a launch. */
 sz_status_t szs_call_reserve_device_words(szs_engine_s *engine, int device, hipStream_t stream, char const **error_message) {
-    sz_status_t const status = szs_buffer_reserve(&engine->device_fused, szs_memory_device_k, device, 256, error_message);
+    sz_status_t const status = szs_buffer_reserve(&engine->device_fused, szs_memory_device_k, device, sizeof(szs_device_words_t), error_message);
     if (status != sz_success_k) return status;
     if (engine->fused_zeroed != engine->device_fused.pointer) {
-        hipError_t const error = hipMemsetAsync(engine->device_fused.pointer, 0, 256, stream);
+        hipError_t const error = hipMemsetAsync(engine->device_fused.pointer, 0, sizeof(szs_device_words_t), stream);
         if (error != hipSuccess) return szs_report_hip(error, error_message);
         engine->fused_zeroed = engine->device_fused.pointer;
     }
@@ -1237,8 +1236,8 @@ sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input
         if (error != hipSuccess) return szs_report_hip(error, error_message);
         engine->events_device = device;
     }
-    /* pinned: the device planner's summary, and behind it the stall flag of the chained tiers */
-    status = szs_buffer_reserve(&engine->pinned_summary, szs_memory_pinned_k, device, 2048, error_message); /* [1024, 2048): the reports of a fused launch */
+    /* pinned: the device planner's summary and the other words the device leaves for the host (szs_pinned_words_t) */
+    status = szs_buffer_reserve(&engine->pinned_summary, szs_memory_pinned_k, device, SZS_PINNED_WORDS_BYTES, error_message);
     if (status != sz_success_k) return status;
 
     call.engine = engine, call.device = device, call.stream = stream;
@@ -1253,10 +1252,10 @@ sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input
         engine->queue_unfit_sequence = 0;
         status = SZS_NOT_DEVICE_PLANNABLE;
         if (planner != 0 && device_plannable(engine, queries) && (symmetric || device_plannable(engine, candidates))) {
-            status = engine->family == szs_family_levenshtein_utf8_k ? szs_cross_device_planned_runes(&call) : SZS_RUNES_ARE_BYTES;
+            status = engine->family == szs_family_levenshtein_utf8_k ? szs_cross_device_planned(&call, 1) : SZS_RUNES_ARE_BYTES;
             if (status == SZS_RUNES_ARE_BYTES) {
                 if (call.ranges) ranges_end(&call), ranges_begin(&call);
-                status = szs_cross_device_planned(&call);
+                status = szs_cross_device_planned(&call, 0);
             }
         }
         if (status == SZS_NOT_DEVICE_PLANNABLE) {
@@ -1264,7 +1263,7 @@ sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input
             status = cross_host_planned(&call);
         }
         ranges_end(&call);
-        uint32_t const raised = *(uint32_t const volatile *)((char const *)engine->pinned_summary.pointer + 960);
+        uint32_t const raised = szs_pinned_words(engine)->queue_unfit;
         if (status != sz_success_k || !engine->queue_unfit_sequence || raised != engine->queue_unfit_sequence) break;
         engine->queue_refused = 1; /* the per-width launches score every cell again */
         if (engine->remembered) engine->remembered->valid = 0;

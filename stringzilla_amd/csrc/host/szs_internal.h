@@ -69,6 +69,13 @@ typedef enum {
     szs_family_smith_waterman_k = 3
 } szs_family_t;
 
+/** What the tiny-token kernel (hip/myers_tiny.hip) made of the previous call of one family: `valid` - it scored a batch of these
+ *  counts that still looked like tiny tokens, so the next call of these counts goes straight there (host/ways_tiny.c). */
+typedef struct szs_tiny_memory_t {
+    int valid;
+    uint32_t q_count, c_count;
+} szs_tiny_memory_t;
+
 typedef struct szs_engine_s {
     uint32_t magic;
     szs_family_t family;
@@ -115,15 +122,14 @@ typedef struct szs_engine_s {
     uint32_t queue_unfit_sequence; /* what the current call's queue launch writes to pinned memory if a query fits none of its tables; 0: no such launch */
     int queue_refused;             /* this call is being scored again without the queue */
     int last_queued;               /* enqueue() issued the persistent launch for the call being finished (the call profile says so) */
-    szs_buffer_t device_fused;     /* device: the two `ready` words of the short launch that plans itself (kernels.h: szs_fused_plan_t) */
+    szs_buffer_t device_fused;     /* device: the `ready` words of the short launch that plans itself, the planner's verdicts
+                                      (dispatch_internal.h: szs_device_words_t) */
     void *fused_zeroed;            /* the allocation of `device_fused` that was zeroed */
     int fused_gave_up;             /* a launch that plans itself ran out of polls on this engine: it is not tried again */
-    int tiny_valid;                /* the previous call of these counts was scored by the tiny-token kernel (hip/myers_tiny.hip): go straight there */
-    uint32_t tiny_q_count, tiny_c_count;
-    int tiny_runes_valid;          /* the same for the codepoint engine: narrowed to byte strings of rune ids, then that kernel (round 6) */
-    uint32_t tiny_runes_q_count, tiny_runes_c_count;
+    szs_tiny_memory_t tiny[2];     /* [0] byte calls, [1] codepoint calls (narrowed to byte strings of rune ids, then that kernel) */
+    int tiny_refused;              /* the kernel REFUSED a batch of tiny[0]'s counts (dense in long strings): calls of these counts skip the
+                                      summary-driven attempt while this counts down - whichever family refused */
     void *narrow_zeroed;           /* the narrow buffer whose head - the table of claimed runes, the totals - holds what the last call left */
-    int tiny_refused;              /* ... or was REFUSED by it (dense in long strings): calls of these counts skip the summary-driven attempt */
     hipEvent_t event_start, event_stop;
     int events_device;
     /* launches of different bit-vector widths fan out over these and fill each other's tails (dispatch.c: enqueue) */
@@ -139,7 +145,7 @@ typedef struct szs_engine_s {
 
     /* device-side planning (hip/planner.hip) */
     szs_buffer_t device_plan_refs; /* device: ascending + descending refs of both sides */
-    szs_buffer_t pinned_summary;   /* pinned: the planner's szs_plan_summary_t */
+    szs_buffer_t pinned_summary;   /* pinned: the planner's szs_plan_summary_t and the words behind it (dispatch_internal.h: szs_pinned_words_t) */
     szs_buffer_t pinned_squares;   /* pinned: a symmetric tiny-token call's sums of squared lengths, one per block of 256 strings */
     uint32_t plan_sequence;        /* echoed by the planner: tells this call's summary from a stale one */
     struct szs_decision_t *remembered; /* the launch shape of the previous device-planned call (speculation), or NULL */

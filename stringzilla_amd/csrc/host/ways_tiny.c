@@ -28,7 +28,7 @@ int szs_tiny_shaped(szs_engine_s const *engine, int symmetric, szs_side_stats_t 
 
 /** The tiny-token kernel refused a recent batch of these counts (cross_tiny): the next sixteen such calls do not try it again. */
 int szs_tiny_recently_refused(szs_engine_s *engine, uint32_t q_count, uint32_t c_count, int count_down) {
-    if (engine->tiny_refused <= 0 || engine->tiny_q_count != q_count || engine->tiny_c_count != c_count) return 0;
+    if (engine->tiny_refused <= 0 || !szs_tiny_counts_match(&engine->tiny[0], q_count, c_count)) return 0;
     if (szs_tuning_get(szs_knob_tiny_k) >= 0) return 0; /* a pinned knob is obeyed every time */
     if (count_down) --engine->tiny_refused;
     return 1;
@@ -43,8 +43,8 @@ int szs_tiny_recently_refused(szs_engine_s *engine, uint32_t q_count, uint32_t c
 sz_status_t szs_cross_tiny(szs_call_t *call, uint32_t planner_mode, szs_plan_summary_t const *seen /* or NULL */, int runes) {
     szs_engine_s *engine = call->engine;
     hipStream_t const stream = call->stream;
-    uint32_t volatile *const unfit = (uint32_t volatile *)((char *)engine->pinned_summary.pointer + 992);
-    unsigned long long volatile *const symbols = (unsigned long long volatile *)((char *)engine->pinned_summary.pointer + 976);
+    uint32_t volatile *const unfit = &szs_pinned_words(engine)->tiny_unfit;
+    unsigned long long volatile *const symbols = szs_pinned_words(engine)->tiny_symbols;
     if (!++engine->plan_sequence) ++engine->plan_sequence;
     uint32_t const sequence = engine->plan_sequence;
     *unfit = 0, symbols[0] = symbols[1] = 0;
@@ -69,7 +69,7 @@ sz_status_t szs_cross_tiny(szs_call_t *call, uint32_t planner_mode, szs_plan_sum
     }
     /* The codepoint engine (round 6; reference: cuda.cuh:3294): one pass ahead of the launch turns both UTF-8 tapes into byte strings of
      * rune ids (hip/utf8.hip: utf8_narrow_kernel) in a buffer of the engine's, and the launch scores THOSE - no transcoding to UTF-32,
-     * no renumbering passes, no planner.  Device staging (cross_device_planned_runes reserved it): a word per string. */
+     * no renumbering passes, no planner.  Device staging (cross_device_planned reserved it): a word per string. */
     uint64_t *const entries = runes ? (uint64_t *)engine->device_transcode.pointer : NULL;
     /* the head of the narrow buffer: the pass's table of claimed runes - it LIVES ON from call to call, zeroed when the buffer is new
      * and after a batch that the pass refused (a full table, perhaps) - and the sides' totals of runes */
@@ -156,13 +156,12 @@ sz_status_t szs_cross_tiny(szs_call_t *call, uint32_t planner_mode, szs_plan_sum
     if (*unfit == sequence) {
         /* refused (a block or span too dense in long strings, a string beyond 255 bytes): remember the counts, so that a stream of
          * such batches does not pay this launch and its wait on every call because their summaries look like words */
-        if (runes) engine->tiny_runes_valid = 0;
-        else engine->tiny_valid = 0;
+        szs_tiny_forget(&engine->tiny[runes]); /* (only this family's record) */
         if (planner_mode == 1) { /* ... a batch whose SUMMARY looked like words (clustered long lines among short ones).  A batch that
                                     came straight here on the previous call's word (mode 5: sentences after words) is judged by its
                                     own summary next time - nothing to remember */
             engine->tiny_refused = 16; /* calls of these counts that go straight to the ordinary path */
-            engine->tiny_q_count = call->q_count, engine->tiny_c_count = call->c_count;
+            engine->tiny[0].q_count = call->q_count, engine->tiny[0].c_count = call->c_count; /* (in the byte record, whichever family refused) */
         }
         return SZS_TINY_NOT_TAKEN;
     }
@@ -183,8 +182,7 @@ sz_status_t szs_cross_tiny(szs_call_t *call, uint32_t planner_mode, szs_plan_sum
     szs_side_stats_t now[2];
     memset(now, 0, sizeof(now));
     now[0].count = call->q_count, now[0].symbols = q_symbols, now[1].count = call->c_count, now[1].symbols = c_symbols;
-    if (runes) engine->tiny_runes_valid = szs_tiny_shaped(engine, call->symmetric, &now[0], &now[1]), engine->tiny_runes_q_count = call->q_count, engine->tiny_runes_c_count = call->c_count;
-    else engine->tiny_valid = szs_tiny_shaped(engine, call->symmetric, &now[0], &now[1]), engine->tiny_q_count = call->q_count, engine->tiny_c_count = call->c_count;
+    szs_tiny_note(&engine->tiny[runes], szs_tiny_shaped(engine, call->symmetric, &now[0], &now[1]), call->q_count, call->c_count);
     if (engine->remembered) engine->remembered->refs_current = 0, engine->remembered->valid = 0; /* another kind of call came between */
     return szs_report(sz_success_k, call->error_message, NULL);
 }
