@@ -66,20 +66,37 @@ namespace szs_hip {
  *  @tparam runes_        symbols are UTF-32 codepoints (strings are `u32` arrays, lengths count runes) and Peq is keyed
  *                        through the workgroup's rune table `keys` instead of directly by byte value.
  */
-template <int words_, int text_dwords_, bool runes_>
+/** The bits of [from, to) that fall into word `w`. */
+__device__ __forceinline__ u32 bits_in_word(u32 from, u32 to, int w) {
+    u32 const low = from > 32u * w ? from : 32u * w, high = to < 32u * w + 32u ? to : 32u * w + 32u;
+    if (low >= high) return 0u;
+    return (high - low == 32u ? ~0u : (1u << (high - low)) - 1u) << (low - 32u * w);
+}
+
+/**
+ *  @tparam paired_  `query` and `second` share the bit-vector (bytes, non-symmetric calls only): from bit 0 up, `pad` phantom
+ *                   rows, the first query's rows, two separator rows, the second query's rows - myers_column's pattern_pair_t.
+ *                   One text stream, one LDS gather and one carry chain per column serve both queries; each lane writes two
+ *                   distances, len(text) + popcount(VP & M) - popcount(VN & M) over either query's rows M.
+ */
+template <int words_, int text_dwords_, bool runes_, bool paired_ = false>
 __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_ref_t const query,
                                                 szs_string_ref_t const *__restrict__ candidates, u32 candidates_count,
                                                 u32 candidate_block, u64 *__restrict__ results, u64 results_row_stride,
                                                 int symmetric, szs_ref_guard_t const &guard, u32 alphabet = 0,
-                                                u32 *claimed_rows = nullptr, u32 blocks_here = 1) {
+                                                u32 *claimed_rows = nullptr, u32 blocks_here = 1, szs_string_ref_t const second = {}) {
+    static_assert(!paired_ || !runes_, "query pairs are a byte-kernel shape");
     constexpr int rows = runes_ ? rune_slots_k : byte_rows_k;
     using layout = peq_layout<words_, rows>;
-    if (guard.enabled && !ref_is_current(guard, 0, query)) { // refs of an earlier call: this query's no longer holds - uniform
+    if (guard.enabled && (!ref_is_current(guard, 0, query) || (paired_ && !ref_is_current(guard, 0, second)))) { // refs of an earlier call - uniform
         if (threadIdx.x == 0) *guard.stale = guard.sequence;
         return;
     }
-    u32 const query_length = query.length;
-    u32 const pad = 32u * words_ - query_length; // phantom low rows
+    u32 const first_length = query.length, second_length = paired_ ? second.length : 0u;
+    u32 const query_length = paired_ ? first_length + second_length : first_length; // pattern symbols in the vector
+    u32 const used_rows = paired_ ? query_length + 2u : query_length;                // ... and the two separator rows
+    u32 const pad = 32u * words_ - used_rows;                                          // phantom low rows
+    u32 const second_row = pad + first_length + 2u;                                    // a pair: the second query's first row
 
     // ---- Peq: zero, then scatter the pattern's bits (LDS atomics; a 128-symbol query is 128 ORs per workgroup).
     for (int i = threadIdx.x; i < layout::total_dwords; i += 256) peq[i] = 0;
@@ -120,12 +137,28 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
     }
     else {
         u8 const *pattern = reinterpret_cast<u8 const *>(query.address);
-        for (u32 i = threadIdx.x; i < query_length; i += 256) {
+        for (u32 i = threadIdx.x; i < first_length; i += 256) {
             u32 const position = pad + i;
             atomicOr(&peq[layout::dword_index(pattern[i], (int)(position >> 5))], 1u << (position & 31));
         }
+        if constexpr (paired_) {
+            u8 const *above = reinterpret_cast<u8 const *>(second.address);
+            for (u32 i = threadIdx.x; i < second_length; i += 256) {
+                u32 const position = second_row + i;
+                atomicOr(&peq[layout::dword_index(above[i], (int)(position >> 5))], 1u << (position & 31));
+            }
+        }
     }
     __syncthreads();
+    // (a pair: the separator rows s0, s1 and the first query's top row, per word - uniform, so scalar registers)
+    pattern_pair_t<words_> boundary;
+    if constexpr (paired_) {
+#pragma unroll
+        for (int w = 0; w < words_; ++w) {
+            boundary.separators[w] = bits_in_word(second_row - 2u, second_row, w);
+            boundary.tops[w] = first_length ? bits_in_word(second_row - 3u, second_row - 2u, w) : 0u;
+        }
+    }
 
     // ---- `blocks_here` candidate blocks against this table, the heaviest (`candidate_block`) first: when a launch is tens of
     //      thousands of workgroups of tiny strings, the table and the round trips to the query are shared by several blocks
@@ -149,8 +182,7 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
     u32 vp[words_], vn[words_];
 #pragma unroll
     for (int w = 0; w < words_; ++w) {
-        u32 const first_bit = 32u * w;
-        vp[w] = first_bit >= pad ? ~0u : (first_bit + 32u <= pad ? 0u : (~0u << (pad - first_bit)));
+        vp[w] = bits_in_word(pad, 32u * words_, w) & ~(paired_ ? boundary.separators[w] : 0u); // separator rows start at 0, like phantom ones
         vn[w] = 0;
     }
 
@@ -158,7 +190,8 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
     auto take = [&](u32 symbol) {
         u32 eq[words_];
         load_match_masks<words_, rows>(peq, !runes_ ? symbol : alphabet ? keys[symbol] : find_rune_slot(keys, symbol), eq);
-        myers_column<words_>(vp, vn, eq);
+        if constexpr (paired_) myers_column<words_>(vp, vn, eq, boundary);
+        else myers_column<words_>(vp, vn, eq);
     };
 
     u32 column = 0;
@@ -186,7 +219,7 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
         // ---- bytes: `raw_low` is text dword `dword`; `ahead[d]` is text dword `dword + 1 + d`, loaded one iteration early.
         // Lanes without a text stream from the query instead (always-valid memory; their symbols are never consumed), so
         // the main loop's reads are index-clamped, not predicated: no branch splits the unrolled batch.
-        u64 const safe_address = text_length ? candidate.address : query.address;
+        u64 const safe_address = text_length ? candidate.address : first_length || !paired_ ? query.address : second.address;
         text_stream_t text(safe_address, text_length);
         if (!text_length) text.valid_dwords = query_length ? 1 : 0;
         u32 raw_low = text.raw(0);
@@ -251,7 +284,21 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
         }
     }
 
-    if (live) {
+    if (live && paired_) {
+        u32 first = text_length, above = text_length;
+#pragma unroll
+        for (int w = 0; w < words_; ++w) {
+            u32 const mine = bits_in_word(pad, pad + first_length, w), theirs = bits_in_word(second_row, 32u * words_, w);
+            first += (u32)__builtin_popcount(vp[w] & mine) - (u32)__builtin_popcount(vn[w] & mine);
+            above += (u32)__builtin_popcount(vp[w] & theirs) - (u32)__builtin_popcount(vn[w] & theirs);
+        }
+        bool const transposed = (symmetric & SZS_LAYOUT_TRANSPOSED) != 0;
+        u64 const one = transposed ? candidate.index : query.index, two = transposed ? candidate.index : second.index;
+        u64 const one_column = transposed ? query.index : candidate.index, two_column = transposed ? second.index : candidate.index;
+        results[one * results_row_stride + one_column] = first;
+        results[two * results_row_stride + two_column] = above;
+    }
+    else if (live) {
         u32 distance = text_length;
 #pragma unroll
         for (int w = 0; w < words_; ++w) distance += (u32)__builtin_popcount(vp[w]) - (u32)__builtin_popcount(vn[w]);
@@ -521,6 +568,10 @@ __device__ __forceinline__ bool fused_prologue(szs_fused_plan_t const &plan, u32
 #ifndef SZS_MYERS_SHORT_WAVES
 #define SZS_MYERS_SHORT_WAVES 1
 #endif
+#ifndef SZS_MYERS_PACK_QUERIES
+#define SZS_MYERS_PACK_QUERIES 1 // 0: one query per workgroup in the fused launch too (the A/B build of query pairs)
+#endif
+constexpr u32 szs_myers_pair_words_k = 10; // the widest bit-vector of two queries: config 2's pairs take 8 to 10 words
 /**
  *  Short queries (up to 256 symbols = 8 words), ANY mix of lengths in ONE launch: the width is a per-workgroup (scalar)
  *  decision, so every query runs at exactly ceil(length / 32) words, and a batch whose queries straddle several widths
@@ -532,7 +583,8 @@ __device__ __forceinline__ void myers_short_body(
     szs_string_ref_t const *__restrict__ queries, szs_string_ref_t const *__restrict__ candidates, u32 candidates_count,
     u32 candidate_blocks, u64 *__restrict__ results, u64 results_row_stride, int symmetric, szs_ref_guard_t guard, u32 alphabet,
     u32 blocks_per_group, szs_fused_plan_t const *fused = nullptr) {
-    __shared__ __attribute__((aligned(16))) u32 peq[peq_layout<8, runes_ ? rune_slots_k : byte_rows_k>::total_dwords];
+    constexpr bool pairs = fused_ && !merged_ && SZS_MYERS_PACK_QUERIES; // (a pair of queries takes up to szs_myers_pair_words_k words)
+    __shared__ __attribute__((aligned(16))) u32 peq[peq_layout<pairs ? szs_myers_pair_words_k : 8, runes_ ? rune_slots_k : byte_rows_k>::total_dwords];
     if constexpr (fused_) {
         static_assert(peq_layout<8, byte_rows_k>::total_dwords >= SZS_FUSED_BINS, "the sort's histogram borrows the masks' LDS");
         if (!fused_prologue(*fused, peq)) return; // the refs `queries` / `candidates` point at exist from here on
@@ -561,26 +613,76 @@ __device__ __forceinline__ void myers_short_body(
         query.length = (u32)__builtin_amdgcn_readfirstlane((int)query.length);
         query.index = (u32)__builtin_amdgcn_readfirstlane((int)query.index);
     }
+    // Query pairs (fused byte launches of one block per workgroup, non-symmetric): slot s of the ceil(Q / 2) slots scores the
+    // descending refs s and s + ceil(Q / 2) - in one bit-vector when that takes no more words than the two apart and at most
+    // szs_myers_pair_words_k, one after the other otherwise (and alone: the middle query of an odd count).
+    szs_string_ref_t second = {0, 0, 0};
+    bool has_second = false;
+    if constexpr (pairs) {
+        if (!fused->symmetric) {
+            u32 const slots = (fused->side[0].count + 1u) / 2u;
+            if (query_slot + slots < fused->side[0].count) {
+                second = queries[query_slot + slots];
+                second.address = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(second.address >> 32)) << 32) |
+                                 (u32)__builtin_amdgcn_readfirstlane((int)(u32)second.address);
+                second.length = (u32)__builtin_amdgcn_readfirstlane((int)second.length);
+                second.index = (u32)__builtin_amdgcn_readfirstlane((int)second.index);
+                has_second = true;
+            }
+        }
+    }
     u32 const words = __builtin_amdgcn_readfirstlane(query.length ? (query.length + 31u) / 32u : 1u);
+    u32 const second_words = second.length ? (second.length + 31u) / 32u : 1u;
+    u32 const pair_words = (query.length + second.length + 2u + 31u) / 32u;
+    if constexpr (pairs) {
+        if (has_second && pair_words <= words + second_words && pair_words <= szs_myers_pair_words_k) {
+#define SZS_MYERS_PAIR_BODY(W)                                                                                         \
+    case W:                                                                                                            \
+        myers_workgroup<W, SZS_MYERS_SHORT_TEXT_DWORDS, false, true>(peq, keys, query, candidates, candidates_count,   \
+                                                                     candidate_block, results, results_row_stride,    \
+                                                                     symmetric, guard, 0u, nullptr, 1u, second);      \
+        return;
+            switch (pair_words) {
+                SZS_MYERS_PAIR_BODY(1)
+                SZS_MYERS_PAIR_BODY(2)
+                SZS_MYERS_PAIR_BODY(3)
+                SZS_MYERS_PAIR_BODY(4)
+                SZS_MYERS_PAIR_BODY(5)
+                SZS_MYERS_PAIR_BODY(6)
+                SZS_MYERS_PAIR_BODY(7)
+                SZS_MYERS_PAIR_BODY(8)
+                SZS_MYERS_PAIR_BODY(9)
+                SZS_MYERS_PAIR_BODY(10)
+            }
+#undef SZS_MYERS_PAIR_BODY
+        }
+    }
 #define SZS_MYERS_BODY(W)                                                                                              \
     case W:                                                                                                            \
         myers_workgroup<W, SZS_MYERS_SHORT_TEXT_DWORDS, runes_>(peq, keys, query, candidates, candidates_count,       \
                                                                 candidate_block, results, results_row_stride,         \
                                                                 symmetric, guard, alphabet, &claimed_rows, blocks_here); \
         break;
-    switch (words) {
-        SZS_MYERS_BODY(1)
-        SZS_MYERS_BODY(2)
-        SZS_MYERS_BODY(3)
-        SZS_MYERS_BODY(4)
-        SZS_MYERS_BODY(5)
-        SZS_MYERS_BODY(6)
-        SZS_MYERS_BODY(7)
-    default: // 8; the host never sends longer queries here
-        myers_workgroup<8, SZS_MYERS_SHORT_TEXT_DWORDS, runes_>(peq, keys, query, candidates, candidates_count,
-                                                                candidate_block, results, results_row_stride, symmetric, guard,
-                                                                alphabet, &claimed_rows, blocks_here);
-        break;
+    // (a pair that does not share a vector: the same switch twice, the table rebuilt in between)
+    for (u32 turn = 0; turn < (has_second ? 2u : 1u); ++turn) {
+        if (turn) {
+            __syncthreads(); // everybody is done with the first query's table
+            query = second;
+        }
+        switch (turn ? second_words : words) {
+            SZS_MYERS_BODY(1)
+            SZS_MYERS_BODY(2)
+            SZS_MYERS_BODY(3)
+            SZS_MYERS_BODY(4)
+            SZS_MYERS_BODY(5)
+            SZS_MYERS_BODY(6)
+            SZS_MYERS_BODY(7)
+        default: // 8; the host never sends longer queries here
+            myers_workgroup<8, SZS_MYERS_SHORT_TEXT_DWORDS, runes_>(peq, keys, query, candidates, candidates_count,
+                                                                    candidate_block, results, results_row_stride, symmetric, guard,
+                                                                    alphabet, &claimed_rows, blocks_here);
+            break;
+        }
     }
 #undef SZS_MYERS_BODY
 }
@@ -1685,11 +1787,13 @@ extern "C" int szs_hip_levenshtein_myers_fused(szs_fused_plan_t const *plan_of_c
     u32 const groups = (candidate_blocks + blocks_per_group - 1) / blocks_per_group;
     if ((u64)queries_count * groups > (1ull << 30)) return (int)hipErrorInvalidValue;
     plan.blocks_per_group = blocks_per_group;
+    // one workgroup per query PAIR (myers_short_body): the slot count is known before the sort
+    u32 const query_slots = SZS_MYERS_PACK_QUERIES && blocks_per_group == 1 && !plan.symmetric ? (queries_count + 1) / 2 : queries_count;
     if (blocks_per_group > 1)
         hipLaunchKernelGGL(levenshtein_myers_short_fused_kernel<true>, dim3(queries_count * groups), dim3(256), 0, static_cast<hipStream_t>(stream), plan,
                            groups, results, results_row_stride, layout);
     else
-        hipLaunchKernelGGL(levenshtein_myers_short_fused_kernel<false>, dim3(queries_count * groups), dim3(256), 0, static_cast<hipStream_t>(stream), plan,
+        hipLaunchKernelGGL(levenshtein_myers_short_fused_kernel<false>, dim3(query_slots * groups), dim3(256), 0, static_cast<hipStream_t>(stream), plan,
                            groups, results, results_row_stride, layout);
     return (int)hipGetLastError();
 }

@@ -77,25 +77,56 @@ __device__ __forceinline__ bool ref_is_current(szs_ref_guard_t const &guard, int
     return to >= from && to - from == ref.length && guard.side[side].base + from == ref.address;
 }
 
-/** One column of the DP matrix: consumes the match masks of one text byte and updates the vertical delta vectors. */
+/** No query boundary inside the bit-vector: the column of a single pattern (every mask below folds to nothing). */
+struct single_pattern_t {
+    __device__ static constexpr u32 separator(int) { return 0; }
+    __device__ static constexpr u32 top(int) { return 0; }
+};
+
+/** Two patterns in one bit-vector (pad, q1, separator rows s0 s1, q2 from bit 0 up): per-word masks, uniform over the
+ *  workgroup (they live in SGPRs).  `separators` marks s0 and s1, `tops` q1's last row.  See myers_column. */
 template <int words_>
-__device__ __forceinline__ void myers_column(u32 (&vp)[words_], u32 (&vn)[words_], u32 const (&eq)[words_]) {
+struct pattern_pair_t {
+    u32 separators[words_], tops[words_];
+    __device__ u32 separator(int w) const { return separators[w]; }
+    __device__ u32 top(int w) const { return tops[w]; }
+};
+
+/** One column of the DP matrix: consumes the match masks of one text byte and updates the vertical delta vectors.
+ *
+ *  With two patterns in the vector (pattern_pair_t) the separator rows carry no Peq bits and start with VP = VN = 0; three
+ *  substitutions keep them so, and cost no instruction (each is the third operand of a v_bitop3):
+ *    X~ = Eq | VN | Msep replaces X in VP' / VN' (the sum and D0 keep plain Eq); HN = VP & D0 & ~Mtop; VN' = HPs & X~ & ~Msep.
+ *  s0 then swallows whatever q1's top row hands up, the add's carry dies in it (VP = 0 there), and s1 - D0 = 0 - gives q2's
+ *  first row HPs = 1, HNs = 0 and carry 0: exactly DP row zero, as bit 0 of the vector gets it. */
+template <int words_, typename boundary_t = single_pattern_t, bool materialise_ = true>
+__device__ __forceinline__ void myers_column(u32 (&vp)[words_], u32 (&vn)[words_], u32 const (&eq)[words_],
+                                             boundary_t const &boundary = {}) {
     u32 carry = 0, hp_below = 0, hn_below = 0;
 #pragma unroll
     for (int w = 0; w < words_; ++w) {
-        u32 const xv = eq[w] | vn[w];
+        u32 xv = eq[w] | vn[w];
+        // (a pair: X~ is ONE full-rate v_bitop3 - left to itself LLVM keeps X for VN' and spends a v_or on X | Msep for VP',
+        // or picks the half-rate v_or3_b32)
+        if constexpr (!std::is_same<boundary_t, single_pattern_t>::value)
+            asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe" : "=v"(xv) : "v"(eq[w]), "v"(vn[w]), "v"(boundary.separator(w)));
         u32 carry_out;
         u32 const sum = __builtin_addc(eq[w] & vp[w], vp[w], carry, &carry_out); // one link of the W-word carry chain
         carry = carry_out;
         u32 const d0 = (sum ^ vp[w]) | eq[w];
         u32 const hp = vn[w] | ~(d0 | vp[w]);
-        u32 const hn = vp[w] & d0;
+        u32 const hn = vp[w] & d0 & ~boundary.top(w);
         // Shift the horizontal deltas up by one row; bit 0 of word 0 takes the constant `+1` of DP row zero.
         u32 const hp_shifted = w == 0 ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
         u32 const hn_shifted = w == 0 ? (hn << 1) : __builtin_amdgcn_alignbit(hn, hn_below, 31);
         hp_below = hp, hn_below = hn;
         vp[w] = hn_shifted | ~(xv | hp_shifted);
-        vn[w] = hp_shifted & xv;
+        vn[w] = hp_shifted & xv & ~boundary.separator(w);
+        // Both new vectors materialised here: without this LLVM folds VP' into the next column's `Eq & VP` and then keeps
+        // `xv | hp_shifted` AND VP' alive - one v_or more per word-step (and scratch in the fused kernel).  Not for one word,
+        // nor where `materialise_` is false (the tiny-token kernel): there the barrier only splits the v_lshl_or_b32 of
+        // `(hp << 1) | 1` into a shift and an or.
+        if constexpr (materialise_ && words_ > 1) asm("" : "+v"(vp[w]), "+v"(vn[w]));
     }
 }
 

@@ -240,7 +240,7 @@ __device__ __forceinline__ void tiny_long_queries(u32 *peq, u32 *out, u64 const 
                     if (4 * d + at < text_length) {
                         u32 eq[words_];
                         masks_of(r, (symbols[d] >> (8 * at)) & 0xFFu, eq);
-                        myers_column<words_>(vp, vn, eq);
+                        myers_column<words_, single_pattern_t, false>(vp, vn, eq);
                     }
             }
             if (column_is_tiny) out16[r * 256u + column] = (unsigned short)distance(text_length, vp, vn);
@@ -273,7 +273,7 @@ __device__ __forceinline__ void tiny_long_queries(u32 *peq, u32 *out, u64 const 
                     four_next = tiny_held_four<registers_>(held, at / 4 + 2);
 #pragma unroll
                     for (u32 i = 0; i < 4; ++i)
-                        if (at + i < held.length) myers_column<words_>(vp, vn, eq_now[i]);
+                        if (at + i < held.length) myers_column<words_, single_pattern_t, false>(vp, vn, eq_now[i]);
 #pragma unroll
                     for (u32 i = 0; i < 4; ++i)
 #pragma unroll
@@ -290,7 +290,7 @@ __device__ __forceinline__ void tiny_long_queries(u32 *peq, u32 *out, u64 const 
                         if (at + i < held.length) {
                             u32 eq[words_];
                             masks_of(table, (four_now >> (8 * i)) & 0xFFu, eq);
-                            myers_column<words_>(vp, vn, eq);
+                            myers_column<words_, single_pattern_t, false>(vp, vn, eq);
                         }
                     four_now = four_next;
                 }
