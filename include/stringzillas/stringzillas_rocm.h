@@ -14,6 +14,9 @@
  *  - szs_rocm_node_*            : one cross-product over the N GPUs of a host, in C (csrc/host/node.c).
  *  - szs_rocm_tuning_set        : the tuning / testing knobs.
  *  - szs_rocm_top_k*            : the k best candidates of every query, without the queries x candidates matrix (csrc/host/top_k.c).
+ *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
+ *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
+ *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
  */
 #ifndef STRINGZILLAS_ROCM_H_
 #define STRINGZILLAS_ROCM_H_
@@ -94,6 +97,42 @@ SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u32tape(void *engine, szs_device_scope
 SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
                                                   sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices,
                                                   void *scores, sz_size_t row_stride, char const **error_message);
+
+/**
+ *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine
+ *  - it supplies `dimensions` and owns the device scratch; any other handle is refused and nothing is written.  Hash matrices are
+ *  row-major `sz_u32_t` with a row stride in BYTES, a multiple of 4 and at least 4 * dimensions, exactly as `szs_fingerprints_*`
+ *  state them (else sz_unexpected_dimensions_k); they may live in device, unified, pinned or plain host memory - what the device
+ *  cannot read is staged a block of queries and a tile of candidates at a time, so a corpus larger than device memory is fine.
+ *
+ *  The comparison is plain equality of the 32-bit hashes: two 0xFFFFFFFF entries (a text shorter than the window) count as equal.
+ *  The Jaccard estimate of a pair is its count divided by `dimensions`; the division is left to the caller.
+ *
+ *  szs_rocm_fingerprint_matches: counts[q * counts_stride (bytes) + c * 4] receives the number of equal dimensions of query q and
+ *  candidate c.  `counts_stride` is a multiple of 4, at least 4 * candidates.  `candidate_hashes` NULL: queries x queries, diagonal
+ *  included (= dimensions); `candidates_count` is then ignored.  Zero queries or zero candidates: success, nothing written.
+ *
+ *  szs_rocm_fingerprint_top_k: the k candidates with the MOST equal dimensions per query, without the matrix.  `k`, `row_stride`,
+ *  `indices` and `matches` follow szs_rocm_top_k: 1 <= k <= 1024 and row_stride >= k (in 8-byte cells), else
+ *  sz_unexpected_dimensions_k; `matches` may be NULL; cells [k, row_stride) are left untouched; equal counts go to the LOWER
+ *  candidate index; a row with fewer than k candidates is completed with index SZ_SIZE_MAX and count 0; zero queries: success,
+ *  nothing written; zero candidates: every row is completed that way; candidate counts beyond 2^32 are fine.  `candidate_hashes`
+ *  NULL: SELF-SEARCH - each query's own index is excluded, identical fingerprints at other indices count.  The `top_k_tile` knob
+ *  caps the candidates of a tile here too.
+ *
+ *  Both calls run on the scope's stream and are synchronous, also when they fail.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fingerprint_matches(szs_fingerprints_t engine, szs_device_scope_t device,
+                                                        sz_u32_t const *query_hashes, sz_size_t query_hashes_stride,
+                                                        sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                                        sz_size_t candidate_hashes_stride, sz_size_t candidates_count,
+                                                        sz_u32_t *counts, sz_size_t counts_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fingerprint_top_k(szs_fingerprints_t engine, szs_device_scope_t device,
+                                                      sz_u32_t const *query_hashes, sz_size_t query_hashes_stride,
+                                                      sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                                      sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_size_t k,
+                                                      sz_size_t *indices, sz_size_t *matches, sz_size_t row_stride,
+                                                      char const **error_message);
 
 /**
  *  Runs the host planner on bare length arrays.  Outputs (all optional):

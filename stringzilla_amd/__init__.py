@@ -418,6 +418,9 @@ class SmithWatermanScores(NeedlemanWunschScores):
     _init = staticmethod(lib.szs_smith_waterman_scores_init)
 
 
+_NO_ROWS = np.zeros(4, dtype=np.uint32)  # where a hash matrix of zero rows points: never NULL, never read
+
+
 class Fingerprints:
     """`Fingerprints(ndim, window_widths=None, alphabet_size=256, seed=0, capabilities=None)` - rolling MinHash /
     Count-Min sketches (`szs_fingerprints_*`; /root/reference/python/README.md:549-590).  Called as
@@ -467,6 +470,140 @@ class Fingerprints:
             return out
         both = device_out[:, :rows].cpu().numpy().view(np.uint32)
         return both[0], both[1]
+
+    def _hashes(self, matrix, name):
+        """-> (pointer, row stride in bytes, rows, GPU index or None) of an `(n, ndim)` matrix of 32-bit hashes with contiguous
+        rows: a `uint32` NumPy array, or an `int32` / `uint32` torch tensor on the host or on a GPU (passed by pointer)."""
+        ndim = self.ndim
+        if isinstance(matrix, np.ndarray):
+            if matrix.ndim != 2 or matrix.shape[1] != ndim or matrix.dtype != np.uint32:
+                raise ValueError(f"`{name}` must be an (n, {ndim}) matrix of uint32 hashes")
+            rows = matrix.shape[0]  # (the strides of an empty or one-row matrix say nothing)
+            if rows and (matrix.strides[1] != 4 or (rows > 1 and (matrix.strides[0] < ndim * 4 or matrix.strides[0] % 4))):
+                raise ValueError(f"`{name}` must have contiguous rows")
+            return matrix.ctypes.data if rows else _NO_ROWS.ctypes.data, matrix.strides[0] if rows > 1 else ndim * 4, rows, None
+        if type(matrix).__module__.partition(".")[0] != "torch" or not hasattr(matrix, "data_ptr"):
+            raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(matrix).__name__}")
+        if matrix.dim() != 2 or matrix.shape[1] != ndim or str(matrix.dtype) not in ("torch.int32", "torch.uint32"):
+            raise ValueError(f"`{name}` must be an (n, {ndim}) matrix of int32 / uint32 hashes")
+        rows = matrix.shape[0]
+        if rows and (matrix.stride(1) != 1 or (rows > 1 and matrix.stride(0) < ndim)):
+            raise ValueError(f"`{name}` must have contiguous rows")
+        if not rows:  # torch gives an empty tensor the pointer 0, and a NULL candidate matrix means self-search to the library
+            return _NO_ROWS.ctypes.data, ndim * 4, 0, None
+        return matrix.data_ptr(), (matrix.stride(0) if rows > 1 else ndim) * 4, rows, matrix.device.index if matrix.is_cuda else None
+
+    def _search_inputs(self, query_hashes, candidate_hashes):
+        queries = self._hashes(query_hashes, "query_hashes")
+        candidates = None if candidate_hashes is None else self._hashes(candidate_hashes, "candidate_hashes")
+        return queries, candidates
+
+    @staticmethod
+    def _drain_torch(gpu_device, *sides):
+        """Whatever torch still has in flight for a GPU tensor runs on TORCH's stream; the search runs on the scope's own.  A tensor
+        on another GPU than the scope's is refused: its pointer means nothing there."""
+        devices = {side[3] for side in sides if side is not None and side[3] is not None}
+        if devices - {gpu_device}:
+            raise ValueError(f"GPU tensors must live on the scope's GPU {gpu_device}, got one on GPU {min(devices - {gpu_device})}")
+        if devices:
+            import torch
+
+            torch.cuda.current_stream(gpu_device).synchronize()
+
+    def matches(self, query_hashes, candidate_hashes=None, device: Optional[DeviceScope] = None, out=None):
+        """Equal dimensions of every (query, candidate) pair of fingerprints (`szs_rocm_fingerprint_matches`): a `(Q, C)` `uint32`
+        matrix.  Inputs are the `(n, ndim)` hash matrices this engine returns - `uint32` NumPy arrays, or `int32` / `uint32` torch
+        tensors on the host or the GPU (passed by pointer), with contiguous rows.  `candidate_hashes` None: the queries against
+        themselves, diagonal included (= `ndim`).  `out`: a `(Q, C)` NumPy array or torch tensor of `int32` / `uint32` cells with
+        contiguous rows, filled and returned.  GPU tensors must live on the scope's GPU.  The Jaccard estimate of a pair is
+        `matches / ndim`: that division stays the caller's.  Equality is plain: two 0xFFFFFFFF hashes (a text shorter than the window) count as equal."""
+        queries, candidates = self._search_inputs(query_hashes, candidate_hashes)
+        import torch
+
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        rows, columns = queries[2], queries[2] if candidates is None else candidates[2]
+        error = "`out` must be a (queries, candidates) matrix of int32 / uint32 cells with contiguous rows"
+        if out is None:
+            out_device = None
+        elif isinstance(out, np.ndarray):
+            if out.shape != (rows, columns) or out.dtype not in (np.uint32, np.int32) or (columns > 1 and out.strides[1] != 4) or out.strides[0] % 4:
+                raise ValueError(error)
+            pointer, stride, out_device = out.ctypes.data, out.strides[0] if rows > 1 else max(columns, 1) * 4, None
+        else:
+            if type(out).__module__.partition(".")[0] != "torch" or not hasattr(out, "data_ptr"):
+                raise ValueError(error)
+            if tuple(out.shape) != (rows, columns) or str(out.dtype) not in ("torch.int32", "torch.uint32") or (
+                    columns > 1 and out.stride(1) != 1):
+                raise ValueError(error)
+            pointer, stride = out.data_ptr(), (out.stride(0) if rows > 1 else max(columns, 1)) * 4
+            out_device = out.device.index if out.is_cuda else None
+        self._drain_torch(gpu_device, queries, candidates, (0, 0, 0, out_device))
+        if out is None:
+            results = torch.empty((max(rows, 1), max(columns, 1)), dtype=torch.int32, device=torch.device("cuda", gpu_device))
+            pointer, stride = results.data_ptr(), max(columns, 1) * 4
+        message = ctypes.c_char_p()
+        status = lib.szs_rocm_fingerprint_matches(
+            self.handle, scope.handle, queries[0], queries[1], rows, None if candidates is None else candidates[0],
+            0 if candidates is None else candidates[1], 0 if candidates is None else columns, pointer, stride, ctypes.byref(message))
+        _abi.check(status, message)
+        if out is not None:
+            return out
+        return results[:rows, :columns].cpu().numpy().view(np.uint32)
+
+    def top_k(self, query_hashes, candidate_hashes=None, k=None, device: Optional[DeviceScope] = None, out=None):
+        """The `k` candidates with the MOST equal dimensions per query (`szs_rocm_fingerprint_top_k`), without the matrix: returns
+        `(indices, matches)`, two `uint64` `(Q, k)` NumPy matrices, or fills `out=(indices, matches)` (NumPy arrays or torch
+        tensors of 8-byte cells, one row stride; `matches` may be None).  Inputs as for `matches()`.  Ties go to the lower candidate
+        index.  `candidate_hashes` None: self-search, each query's own index excluded (identical fingerprints at other indices
+        count).  A row with fewer than `k` candidates ends in index 2**64 - 1 and count 0.  The Jaccard estimate of a hit is
+        `matches / ndim`: that division stays the caller's."""
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError(f"k must be an integer within [1, 1024], got {k!r}")
+        k = int(k)
+        queries, candidates = self._search_inputs(query_hashes, candidate_hashes)
+        import torch
+
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        rows = queries[2]
+        out_devices = []
+
+        def cells_of(matrix, name):  # -> (pointer, row stride in cells)
+            if matrix is None:
+                return None, None
+            if isinstance(matrix, np.ndarray):
+                shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
+                pointer = matrix.ctypes.data
+            else:
+                shape, itemsize, strides, pointer = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr()
+                if matrix.is_cuda:
+                    out_devices.append((0, 0, 0, matrix.device.index))
+            if shape != (rows, k) or itemsize != 8 or (k > 1 and strides[1] != 1):
+                raise ValueError(f"`out` {name} must be a (rows, k) matrix of 8-byte cells with contiguous rows")
+            return pointer, strides[0] if rows > 1 else k
+
+        if out is not None:
+            indices_pointer, stride = cells_of(out[0], "indices")
+            matches_pointer, matches_stride = cells_of(out[1], "matches")
+            if indices_pointer is None:
+                raise ValueError("`out` indices must not be None")
+            if matches_pointer is not None and matches_stride != stride:
+                raise ValueError("`out` indices and matches must share one row stride")
+        self._drain_torch(gpu_device, queries, candidates, *out_devices)
+        if out is None:
+            both = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+            indices_pointer, matches_pointer, stride = both[0].data_ptr(), both[1].data_ptr(), k
+        message = ctypes.c_char_p()
+        status = lib.szs_rocm_fingerprint_top_k(
+            self.handle, scope.handle, queries[0], queries[1], rows, None if candidates is None else candidates[0],
+            0 if candidates is None else candidates[1], 0 if candidates is None else candidates[2], k, indices_pointer,
+            matches_pointer, stride, ctypes.byref(message))
+        _abi.check(status, message)
+        if out is not None:
+            return out
+        host = both[:, :rows].cpu().numpy().view(np.uint64)
+        return host[0], host[1]
 
     def __del__(self):
         handle = getattr(self, "handle", None)

@@ -131,6 +131,10 @@ SIGNATURES = {
     "szs_rocm_node_scores_u32tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_node_scores_u64tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_top_k": _TOP_K, "szs_rocm_top_k_u32tape": _TOP_K, "szs_rocm_top_k_u64tape": _TOP_K,
+    "szs_rocm_fingerprint_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t,
+                                             c_void_p, c_size_t, ERR]),
+    "szs_rocm_fingerprint_top_k": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t,
+                                           c_void_p, c_void_p, c_size_t, ERR]),
 }
 
 REFERENCE_SYMBOLS = [name for name in SIGNATURES if not name.startswith("szs_rocm_")]  # the reference's 41

@@ -250,6 +250,21 @@ int szs_hip_top_k_scan(uint64_t const *cells, uint64_t cells_stride, uint32_t ro
 int szs_hip_top_k_emit(uint64_t const *lists, uint32_t rows, uint32_t k, uint64_t *indices, uint64_t *scores, uint64_t stride,
                        int descending, void *stream);
 
+/**
+ *  Equal dimensions of MinHash fingerprints (hip/fingerprint_matches.hip; host/fingerprint_search.c):
+ *  cells[q][c] = #{ d < dimensions : queries[q][d] == candidates[c][d] } for q < rows, c < columns.  Both hash matrices are
+ *  row-major u32 with a row stride in BYTES (a multiple of 4, at least 4 * dimensions), device-accessible.  Plain equality: two
+ *  0xFFFFFFFF entries count as equal.  The _u32 launcher writes 4-byte cells, its `cells_stride_bytes` in bytes (a multiple of 4):
+ *  the matrix call.  The _u64 launcher writes 8-byte cells, its `cells_stride` in cells: a scratch tile that szs_hip_top_k_scan
+ *  folds unchanged with `descending` = 1.  rows <= 65535 * 64; any dimensions >= 1; edges need not be multiples of anything.
+ */
+int szs_hip_fingerprint_matches_u32(uint32_t const *queries, uint64_t queries_stride, uint32_t rows, uint32_t const *candidates,
+                                    uint64_t candidates_stride, uint32_t columns, uint32_t dimensions, uint32_t *cells,
+                                    uint64_t cells_stride_bytes, void *stream);
+int szs_hip_fingerprint_matches_u64(uint32_t const *queries, uint64_t queries_stride, uint32_t rows, uint32_t const *candidates,
+                                    uint64_t candidates_stride, uint32_t columns, uint32_t dimensions, uint64_t *cells,
+                                    uint64_t cells_stride, void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {

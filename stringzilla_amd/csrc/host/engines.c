@@ -289,3 +289,21 @@ sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_s
                                    sz_size_t row_stride, char const **error_message) {
     SZS_TOP_K_BODY(input_from_u64tape)
 }
+
+/* ---- fingerprint search (host/fingerprint_search.c) ------------------------------------------------------------------- */
+
+sz_status_t szs_rocm_fingerprint_matches(szs_fingerprints_t engine, szs_device_scope_t device, sz_u32_t const *query_hashes,
+                                         sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                         sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_u32_t *counts,
+                                         sz_size_t counts_stride, char const **error_message) {
+    return szs_fingerprints_matches((szs_fingerprints_s *)engine, (szs_scope_s *)device, query_hashes, query_hashes_stride, queries_count,
+                                    candidate_hashes, candidate_hashes_stride, candidates_count, counts, counts_stride, error_message);
+}
+sz_status_t szs_rocm_fingerprint_top_k(szs_fingerprints_t engine, szs_device_scope_t device, sz_u32_t const *query_hashes,
+                                       sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                       sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_size_t k, sz_size_t *indices,
+                                       sz_size_t *matches, sz_size_t row_stride, char const **error_message) {
+    return szs_fingerprints_top_k((szs_fingerprints_s *)engine, (szs_scope_s *)device, query_hashes, query_hashes_stride, queries_count,
+                                  candidate_hashes, candidate_hashes_stride, candidates_count, k, indices, matches, row_stride,
+                                  error_message);
+}

@@ -16,25 +16,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define SZS_FINGERPRINTS_MAGIC 0x535A5346u
-
-struct szs_fingerprints_s {
-    uint32_t magic;
-    uint32_t dimensions;
-    uint32_t *widths;      /* [dimensions] */
-    double *parameters;    /* [4][dimensions]: multipliers, modulos, reciprocals, complements */
-    uint32_t widest;
-
-    int device;            /* scratch follows the device of the last call */
-    int parameters_device; /* device the parameters were uploaded to, or -1 */
-    szs_buffer_t device_parameters; /* [4][dimensions] doubles, then [dimensions] u32 widths */
-    szs_buffer_t host_scratch;      /* addresses, lengths */
-    szs_buffer_t pinned_staging;    /* refs, prefixes, segment owners, merge list; offsets downloads */
-    szs_buffer_t device_tables;     /* the same tables on the device */
-    szs_buffer_t device_partials;   /* (double, u32) per (segment of a multi-segment text, dimension) */
-    szs_buffer_t device_outputs;    /* dense staging when the caller's outputs are not device-resident */
-};
-
 static uint64_t splitmix64(uint64_t state) { /* serial.hpp:44-50; https://prng.di.unimi.it/splitmix64.c */
     state += 0x9E3779B97F4A7C15ull;
     uint64_t z = state;
@@ -102,7 +83,21 @@ static void release_device_state(szs_fingerprints_s *engine) {
     szs_buffer_release(&engine->device_tables);
     szs_buffer_release(&engine->device_partials);
     szs_buffer_release(&engine->device_outputs);
+    szs_buffer_release(&engine->device_search_hashes);
+    szs_buffer_release(&engine->device_search_scratch);
+    szs_buffer_release(&engine->device_search_lists);
+    szs_buffer_release(&engine->device_search_out);
     engine->parameters_device = -1;
+}
+
+void szs_fingerprints_follow_device(szs_fingerprints_s *engine, int device) {
+    if (engine->device == device) return; /* scratch follows the device of the call */
+    if (engine->device >= 0) {
+        (void)hipSetDevice(engine->device);
+        release_device_state(engine);
+        (void)hipSetDevice(device);
+    }
+    engine->device = device;
 }
 
 void szs_fingerprints_destroy(szs_fingerprints_s *engine) {
@@ -140,14 +135,7 @@ sz_status_t szs_fingerprints_call(szs_fingerprints_s *engine, szs_scope_s *scope
     if (min_hashes_stride < row_bytes || min_counts_stride < row_bytes || min_hashes_stride % 4 || min_counts_stride % 4)
         return szs_report(sz_unexpected_dimensions_k, error_message, NULL);
 
-    if (engine->device != device) { /* scratch follows the device of the call */
-        if (engine->device >= 0) {
-            (void)hipSetDevice(engine->device);
-            release_device_state(engine);
-            (void)hipSetDevice(device);
-        }
-        engine->device = device;
-    }
+    szs_fingerprints_follow_device(engine, device);
     hipError_t error = hipSuccess;
     if (engine->parameters_device != device) { /* [4][dimensions] doubles followed by the widths, once per device */
         size_t const doubles_bytes = (size_t)dimensions * 4 * sizeof(double);

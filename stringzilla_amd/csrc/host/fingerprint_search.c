@@ -1,0 +1,235 @@
+/*
+ *  fingerprint_search.c - what MinHash fingerprints are for: the equal dimensions of every (query, candidate) pair
+ *  (szs_rocm_fingerprint_matches) and the k candidates with the most of them per query (szs_rocm_fingerprint_top_k);
+ *  include/stringzillas/stringzillas_rocm.h, DESIGN.md section 4.7.
+ *
+ *  Both calls are cut into blocks of queries x tiles of candidates.  hip/fingerprint_matches.hip counts a tile; the matrix call
+ *  writes it where the caller wants it, the search writes 8-byte cells into a device scratch matrix that hip/top_k.hip folds into
+ *  each query's running list - the very selection the similarity engines use (host/top_k.c), descending.  Hash matrices the device
+ *  cannot read (plain host memory) are staged: the query block once per block, the candidate rows once per tile, so a corpus of
+ *  any size passes through a bounded device buffer.  Everything runs on the scope's stream; both calls are synchronous.
+ */
+#include "szs_internal.h"
+
+#define SZS_SEARCH_SCRATCH_CELLS ((size_t)16 << 20) /* as host/top_k.c: a tile the fold re-reads from the Infinity Cache */
+#define SZS_SEARCH_LIST_BYTES ((size_t)128 << 20)   /* running lists of one block of queries */
+#define SZS_SEARCH_MOST_ROWS ((size_t)1 << 18)      /* per side of a tile */
+#define SZS_SEARCH_WORKGROUPS 2048u                 /* the scan wants ~8 workgroups per CU: rows are split into segments below that */
+#define SZS_SEARCH_STAGE_BYTES ((size_t)256 << 20)  /* per side: hashes staged from memory the device cannot read */
+
+static size_t at_most(size_t value, size_t limit) { return value < limit ? value : limit; }
+static size_t at_least_one(size_t value) { return value ? value : 1; }
+
+/** What both calls check before anything is touched: the strides first, then the engine, then the strides against its dimensions. */
+static sz_status_t vet(szs_fingerprints_s const *engine, sz_size_t query_hashes_stride, sz_u32_t const *candidate_hashes,
+                       sz_size_t candidate_hashes_stride, char const **error_message) {
+    if (query_hashes_stride % 4 || (candidate_hashes && candidate_hashes_stride % 4))
+        return szs_report(sz_unexpected_dimensions_k, error_message, "Hash strides are in bytes and must be multiples of 4");
+    if (!engine || engine->magic != SZS_FINGERPRINTS_MAGIC)
+        return szs_report(sz_status_unknown_k, error_message, "Engine must be an initialized fingerprints engine");
+    size_t const row_bytes = (size_t)engine->dimensions * sizeof(uint32_t);
+    if (query_hashes_stride < row_bytes || (candidate_hashes && candidate_hashes_stride < row_bytes))
+        return szs_report(sz_unexpected_dimensions_k, error_message, "Hash strides must be at least 4 * dimensions bytes");
+    return sz_success_k;
+}
+
+/** One side of a call: where its rows are, and how a stretch of them reaches the device. */
+typedef struct {
+    char const *rows;
+    size_t stride, count;
+    int device_accessible;
+    char *staging; /* dense rows of `row_bytes` in device memory, when not device-accessible */
+} szs_hash_side_t;
+
+/** Rows [first, first + count) for a kernel: in place, or copied into the side's staging area behind whatever still reads it. */
+static hipError_t side_rows(szs_hash_side_t const *side, size_t first, size_t count, size_t row_bytes, hipStream_t stream,
+                            uint32_t const **rows, uint64_t *stride) {
+    if (side->device_accessible) {
+        *rows = (uint32_t const *)(side->rows + first * side->stride), *stride = side->stride;
+        return hipSuccess;
+    }
+    *rows = (uint32_t const *)side->staging, *stride = row_bytes;
+    return hipMemcpy2DAsync(side->staging, row_bytes, side->rows + first * side->stride, side->stride, row_bytes, count, hipMemcpyDefault,
+                            stream);
+}
+
+/** Reserves the staging areas of the sides that need one: [query block][candidate tile], each on a 256-byte boundary. */
+static sz_status_t reserve_staging(szs_fingerprints_s *engine, int device, szs_hash_side_t *queries, size_t block, szs_hash_side_t *pool,
+                                   size_t tile, size_t row_bytes, char const **error_message) {
+    size_t const query_bytes = queries->device_accessible ? 0 : (block * row_bytes + 255) / 256 * 256;
+    size_t const pool_bytes = pool->device_accessible ? 0 : tile * row_bytes;
+    if (!(query_bytes + pool_bytes)) return sz_success_k;
+    sz_status_t const status = szs_buffer_reserve(&engine->device_search_hashes, szs_memory_device_k, device, query_bytes + pool_bytes, error_message);
+    if (status != sz_success_k) return status;
+    queries->staging = (char *)engine->device_search_hashes.pointer;
+    pool->staging = queries->staging + query_bytes;
+    return sz_success_k;
+}
+
+sz_status_t szs_fingerprints_matches(szs_fingerprints_s *engine, szs_scope_s *scope, sz_u32_t const *query_hashes,
+                                     sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                     sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_u32_t *counts,
+                                     sz_size_t counts_stride, char const **error_message) {
+    sz_status_t status = vet(engine, query_hashes_stride, candidate_hashes, candidate_hashes_stride, error_message);
+    if (status != sz_success_k) return status;
+    int const self = candidate_hashes == NULL;
+    size_t const q_count = queries_count, c_count = self ? queries_count : candidates_count;
+    if (!q_count || !c_count) return szs_report(sz_success_k, error_message, NULL);
+    if (!query_hashes) return szs_report(sz_status_unknown_k, error_message, "Query hashes must not be null");
+    if (!counts) return szs_report(sz_status_unknown_k, error_message, "Counts must not be null");
+    if (counts_stride % 4 || counts_stride / sizeof(uint32_t) < c_count)
+        return szs_report(sz_unexpected_dimensions_k, error_message, "The counts stride is in bytes: a multiple of 4, at least 4 * candidates");
+
+    int device = 0;
+    hipStream_t stream = NULL;
+    status = szs_scope_bind_gpu(scope, &device, &stream, error_message);
+    if (status != sz_success_k) return status;
+    szs_fingerprints_follow_device(engine, device);
+
+    uint32_t const dimensions = engine->dimensions;
+    size_t const row_bytes = (size_t)dimensions * sizeof(uint32_t);
+    szs_hash_side_t queries = {(char const *)query_hashes, query_hashes_stride, q_count, szs_classify_pointer(query_hashes).device_accessible, NULL};
+    szs_hash_side_t pool = queries;
+    if (!self) {
+        pool.rows = (char const *)candidate_hashes, pool.stride = candidate_hashes_stride, pool.count = c_count;
+        pool.device_accessible = szs_classify_pointer(candidate_hashes).device_accessible;
+    }
+    int const direct = szs_classify_pointer(counts).device_accessible;
+
+    /* blocks of queries x tiles of candidates: within the kernel's grid, the staging areas and - for counts the device cannot
+     * write - a dense scratch tile that is copied out in one piece */
+    size_t block = at_most(q_count, (size_t)1 << 20), tile = at_most(c_count, (size_t)1 << 22);
+    if (!queries.device_accessible) block = at_most(block, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
+    if (!pool.device_accessible) tile = at_most(tile, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
+    if (!direct) {
+        block = at_most(block, 4096);
+        tile = at_most(tile, 2 * SZS_SEARCH_SCRATCH_CELLS / block);
+    }
+    status = reserve_staging(engine, device, &queries, block, &pool, tile, row_bytes, error_message);
+    if (status == sz_success_k && !direct)
+        status = szs_buffer_reserve(&engine->device_search_scratch, szs_memory_device_k, device, block * tile * sizeof(uint32_t), error_message);
+    if (status != sz_success_k) return status;
+
+    hipError_t error = hipSuccess;
+    for (size_t q0 = 0; q0 < q_count && error == hipSuccess; q0 += block) {
+        size_t const rows = at_most(q_count - q0, block);
+        uint32_t const *query_rows = NULL, *pool_rows = NULL;
+        uint64_t query_stride = 0, pool_stride = 0;
+        error = side_rows(&queries, q0, rows, row_bytes, stream, &query_rows, &query_stride);
+        for (size_t c0 = 0; c0 < c_count && error == hipSuccess; c0 += tile) {
+            size_t const columns = at_most(c_count - c0, tile);
+            error = side_rows(&pool, c0, columns, row_bytes, stream, &pool_rows, &pool_stride);
+            if (error != hipSuccess) break;
+            uint32_t *const target = direct ? (uint32_t *)((char *)counts + q0 * counts_stride) + c0 : (uint32_t *)engine->device_search_scratch.pointer;
+            size_t const target_stride = direct ? counts_stride : columns * sizeof(uint32_t);
+            error = (hipError_t)szs_hip_fingerprint_matches_u32(query_rows, query_stride, (uint32_t)rows, pool_rows, pool_stride, (uint32_t)columns,
+                                                                dimensions, target, target_stride, stream);
+            if (error == hipSuccess && !direct)
+                error = hipMemcpy2DAsync((char *)counts + q0 * counts_stride + c0 * sizeof(uint32_t), counts_stride, target, target_stride,
+                                         columns * sizeof(uint32_t), rows, hipMemcpyDefault, stream);
+        }
+    }
+    hipError_t const drained = hipStreamSynchronize(stream); /* synchronous, also when it fails */
+    if (error == hipSuccess) error = drained;
+    if (error != hipSuccess) return szs_report_hip(error, error_message);
+    return szs_report(sz_success_k, error_message, NULL);
+}
+
+sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scope, sz_u32_t const *query_hashes,
+                                   sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                   sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_size_t k, sz_size_t *indices,
+                                   sz_size_t *matches, sz_size_t row_stride, char const **error_message) {
+    if (k < 1 || k > SZS_TOP_K_MOST || row_stride < k)
+        return szs_report(sz_unexpected_dimensions_k, error_message, "k must be within [1, 1024] and row_stride at least k");
+    sz_status_t status = vet(engine, query_hashes_stride, candidate_hashes, candidate_hashes_stride, error_message);
+    if (status != sz_success_k) return status;
+    if (!queries_count) return szs_report(sz_success_k, error_message, NULL);
+    if (!query_hashes) return szs_report(sz_status_unknown_k, error_message, "Query hashes must not be null");
+    if (!indices) return szs_report(sz_status_unknown_k, error_message, "Indices must not be null");
+
+    int device = 0;
+    hipStream_t stream = NULL;
+    status = szs_scope_bind_gpu(scope, &device, &stream, error_message);
+    if (status != sz_success_k) return status;
+    szs_fingerprints_follow_device(engine, device);
+
+    int const self = candidate_hashes == NULL;
+    size_t const q_count = queries_count, c_count = self ? queries_count : candidates_count;
+    uint32_t const dimensions = engine->dimensions;
+    size_t const row_bytes = (size_t)dimensions * sizeof(uint32_t);
+    szs_hash_side_t queries = {(char const *)query_hashes, query_hashes_stride, q_count, szs_classify_pointer(query_hashes).device_accessible, NULL};
+    szs_hash_side_t pool = queries;
+    if (!self) {
+        pool.rows = (char const *)candidate_hashes, pool.stride = candidate_hashes_stride, pool.count = c_count;
+        pool.device_accessible = szs_classify_pointer(candidate_hashes).device_accessible;
+    }
+    size_t const width = szs_hip_top_k_width((uint32_t)k), list_bytes = 2 * width * sizeof(uint64_t);
+
+    /* the budget of host/top_k.c - blocks of queries whose lists fit, tiles of candidates whose counts fit the scratch matrix, row
+     * segments so that the scan fills the GPU - and on top of it the staging areas of hashes the device cannot read */
+    size_t block = at_most(q_count, SZS_SEARCH_MOST_ROWS);
+    block = at_most(block, SZS_SEARCH_LIST_BYTES / list_bytes);
+    size_t const wide = c_count < 4096 ? at_least_one(c_count) : 4096;
+    block = at_most(block, SZS_SEARCH_SCRATCH_CELLS / wide);
+    if (!queries.device_accessible) block = at_most(block, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
+    size_t tile = at_most(SZS_SEARCH_SCRATCH_CELLS / block, SZS_SEARCH_MOST_ROWS);
+    if (!pool.device_accessible) tile = at_most(tile, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
+    int const knob = szs_tuning_get(szs_knob_top_k_tile_k);
+    if (knob > 0 && (size_t)knob < tile) tile = (size_t)knob;
+    if (tile > c_count) tile = at_least_one(c_count);
+    size_t segments = (SZS_SEARCH_WORKGROUPS + block - 1) / block;
+    if (segments > tile / 4096) segments = tile / 4096;
+    if (segments < 1) segments = 1;
+    size_t const partial_bytes = segments > 1 ? block * segments * list_bytes : 0;
+
+    status = reserve_staging(engine, device, &queries, block, &pool, tile, row_bytes, error_message);
+    if (status == sz_success_k)
+        status = szs_buffer_reserve(&engine->device_search_scratch, szs_memory_device_k, device, block * tile * sizeof(uint64_t), error_message);
+    if (status == sz_success_k)
+        status = szs_buffer_reserve(&engine->device_search_lists, szs_memory_device_k, device, block * list_bytes + partial_bytes, error_message);
+    /* outputs a kernel can write go straight there; others (plain host memory) are staged densely and copied in one piece */
+    int const direct = szs_classify_pointer(indices).device_accessible && (!matches || szs_classify_pointer(matches).device_accessible);
+    if (status == sz_success_k && !direct)
+        status = szs_buffer_reserve(&engine->device_search_out, szs_memory_device_k, device, 2 * block * k * sizeof(uint64_t), error_message);
+    if (status != sz_success_k) return status;
+    uint64_t *const lists = (uint64_t *)engine->device_search_lists.pointer;
+    uint64_t *const partials = lists + block * 2 * width;
+    uint64_t *const cells = (uint64_t *)engine->device_search_scratch.pointer;
+
+    hipError_t error = hipSuccess;
+    for (size_t q0 = 0; q0 < q_count && error == hipSuccess; q0 += block) {
+        size_t const rows = at_most(q_count - q0, block);
+        uint32_t const *query_rows = NULL, *pool_rows = NULL;
+        uint64_t query_stride = 0, pool_stride = 0;
+        error = side_rows(&queries, q0, rows, row_bytes, stream, &query_rows, &query_stride);
+        if (error == hipSuccess) error = hipMemsetAsync(lists, 0xFF, rows * list_bytes, stream); /* empty lists */
+        for (size_t c0 = 0; c0 < c_count && error == hipSuccess; c0 += tile) {
+            size_t const columns = at_most(c_count - c0, tile);
+            error = side_rows(&pool, c0, columns, row_bytes, stream, &pool_rows, &pool_stride);
+            if (error == hipSuccess)
+                error = (hipError_t)szs_hip_fingerprint_matches_u64(query_rows, query_stride, (uint32_t)rows, pool_rows, pool_stride,
+                                                                    (uint32_t)columns, dimensions, cells, columns, stream);
+            if (error == hipSuccess)
+                error = (hipError_t)szs_hip_top_k_scan(cells, columns, (uint32_t)rows, (uint32_t)columns, c0, self ? q0 : ~(uint64_t)0, lists,
+                                                       partials, (uint32_t)segments, (uint32_t)k, 1 /* most matches first */, stream);
+        }
+        if (error != hipSuccess) break;
+        if (direct)
+            error = (hipError_t)szs_hip_top_k_emit(lists, (uint32_t)rows, (uint32_t)k, (uint64_t *)indices + q0 * row_stride,
+                                                   matches ? (uint64_t *)matches + q0 * row_stride : NULL, row_stride, 1, stream);
+        else {
+            uint64_t *const staged_indices = (uint64_t *)engine->device_search_out.pointer, *const staged_matches = staged_indices + rows * k;
+            error = (hipError_t)szs_hip_top_k_emit(lists, (uint32_t)rows, (uint32_t)k, staged_indices, staged_matches, k, 1, stream);
+            if (error == hipSuccess)
+                error = hipMemcpy2DAsync((uint64_t *)indices + q0 * row_stride, row_stride * sizeof(uint64_t), staged_indices,
+                                         k * sizeof(uint64_t), k * sizeof(uint64_t), rows, hipMemcpyDefault, stream);
+            if (error == hipSuccess && matches)
+                error = hipMemcpy2DAsync((uint64_t *)matches + q0 * row_stride, row_stride * sizeof(uint64_t), staged_matches,
+                                         k * sizeof(uint64_t), k * sizeof(uint64_t), rows, hipMemcpyDefault, stream);
+        }
+    }
+    hipError_t const drained = hipStreamSynchronize(stream); /* synchronous, also when it fails */
+    if (error == hipSuccess) error = drained;
+    if (error != hipSuccess) return szs_report_hip(error, error_message);
+    return szs_report(sz_success_k, error_message, NULL);
+}

@@ -192,6 +192,32 @@ sz_status_t szs_gather_strings(szs_input_t const *input, void const *offsets, ui
 /* ---- fingerprint engines (fingerprint_engines.c) --------------------------------------------------------------------------- */
 
 typedef struct szs_fingerprints_s szs_fingerprints_s;
+
+#define SZS_FINGERPRINTS_MAGIC 0x535A5346u
+
+struct szs_fingerprints_s {
+    uint32_t magic;
+    uint32_t dimensions;
+    uint32_t *widths;      /* [dimensions] */
+    double *parameters;    /* [4][dimensions]: multipliers, modulos, reciprocals, complements */
+    uint32_t widest;
+
+    int device;            /* scratch follows the device of the last call */
+    int parameters_device; /* device the parameters were uploaded to, or -1 */
+    szs_buffer_t device_parameters; /* [4][dimensions] doubles, then [dimensions] u32 widths */
+    szs_buffer_t host_scratch;      /* addresses, lengths */
+    szs_buffer_t pinned_staging;    /* refs, prefixes, segment owners, merge list; offsets downloads */
+    szs_buffer_t device_tables;     /* the same tables on the device */
+    szs_buffer_t device_partials;   /* (double, u32) per (segment of a multi-segment text, dimension) */
+    szs_buffer_t device_outputs;    /* dense staging when the caller's outputs are not device-resident */
+
+    /* fingerprint search (host/fingerprint_search.c): buffers of their own, so a search never disturbs a hashing call */
+    szs_buffer_t device_search_hashes;  /* device: the query block, then the candidate tile, of hashes that live in plain host memory */
+    szs_buffer_t device_search_scratch; /* device: the tile of match counts (8-byte cells: top-k; 4-byte cells: a staged matrix) */
+    szs_buffer_t device_search_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
+    szs_buffer_t device_search_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
+};
+
 sz_status_t szs_fingerprints_create(sz_size_t dimensions, sz_size_t alphabet_size, sz_size_t const *window_widths,
                                     sz_size_t window_widths_count, sz_u64_t seed, sz_capability_t capabilities,
                                     szs_fingerprints_t *engine, char const **error_message);
@@ -199,6 +225,21 @@ sz_status_t szs_fingerprints_call(szs_fingerprints_s *engine, szs_scope_s *scope
                                   sz_u32_t *min_hashes, sz_size_t min_hashes_stride, sz_u32_t *min_counts,
                                   sz_size_t min_counts_stride, char const **error_message);
 void szs_fingerprints_destroy(szs_fingerprints_s *engine);
+/** Moves the engine's device scratch to `device` (releases what lives on another one); fingerprint_engines.c. */
+void szs_fingerprints_follow_device(szs_fingerprints_s *engine, int device);
+
+/* ---- fingerprint search (fingerprint_search.c) --------------------------------------------------------------------------- */
+
+/** `candidate_hashes` NULL: the queries against themselves, diagonal included. */
+sz_status_t szs_fingerprints_matches(szs_fingerprints_s *engine, szs_scope_s *scope, sz_u32_t const *query_hashes,
+                                     sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                     sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_u32_t *counts,
+                                     sz_size_t counts_stride, char const **error_message);
+/** `candidate_hashes` NULL: self-search (each query against all queries but itself). */
+sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scope, sz_u32_t const *query_hashes,
+                                   sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
+                                   sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_size_t k, sz_size_t *indices,
+                                   sz_size_t *matches, sz_size_t row_stride, char const **error_message);
 
 /* ---- planner (plan.c) - pure host logic, unit-tested without a GPU through the szs_rocm_plan_* exports ------------ */
 
