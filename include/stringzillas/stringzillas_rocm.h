@@ -14,6 +14,8 @@
  *  - szs_rocm_node_*            : one cross-product over the N GPUs of a host, in C (csrc/host/node.c).
  *  - szs_rocm_tuning_set        : the tuning / testing knobs.
  *  - szs_rocm_top_k*            : the k best candidates of every query, without the queries x candidates matrix (csrc/host/top_k.c).
+ *  - szs_rocm_rerank*           : exact scores of LISTED candidates per query - what verifies the hits of a coarse search (top-k's own
+ *    `indices`, a fingerprint search, any outside candidate generator) without a queries x candidates matrix (csrc/host/rerank.c).
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -97,6 +99,41 @@ SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u32tape(void *engine, szs_device_scope
 SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
                                                   sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices,
                                                   void *scores, sz_size_t row_stride, char const **error_message);
+
+/**
+ *  Rerank: the exact scores of the candidates an index row LISTS per query, in one call -
+ *      scores[q * row_stride + r] = score(queries[q], candidates[indices[q * row_stride + r]])   for r < k,
+ *  8-byte cells of the engine's own type (`sz_size_t` distances, `sz_ssize_t` scores): exactly the value the matrix call would put
+ *  in that cell.  `indices` and `scores` share `row_stride`, in 8-byte cells - the layout szs_rocm_top_k* and
+ *  szs_rocm_fingerprint_top_k write, so their `indices` output is this call's input unchanged.
+ *
+ *  `engine`: a Levenshtein, Levenshtein UTF-8, Needleman-Wunsch or Smith-Waterman engine; any other handle is refused and nothing
+ *  is written.  An index equal to SZ_SIZE_MAX is the empty slot those calls emit: its score cell receives 0 and no string is
+ *  touched.  Any other index >= the candidates' count fails the whole call with sz_unexpected_dimensions_k, and no string or offset
+ *  is ever read through it: indices the host can read are validated before anything is launched, indices only the device can read
+ *  are checked by the kernel before every use.  After a failed call the contents of `scores` are unspecified.  Duplicate indices
+ *  within a row, and the same candidate in many rows, are fine.
+ *
+ *  `candidates` NULL: the indices refer to `queries` themselves - the self-search form of top-k; no index is excluded.
+ *
+ *  k >= 1, with no upper bound, and row_stride >= k, else sz_unexpected_dimensions_k; score cells [k, row_stride) are left
+ *  untouched.  Zero queries: success, nothing written.  `indices` and `scores` must not be NULL.  Both may live in host, pinned,
+ *  unified or device memory, as may the strings' offsets.  The call runs on the scope's stream and is synchronous, also when it fails.
+ *
+ *  Rows of a unit-cost byte Levenshtein engine whose query has at most 256 bytes are scored by ONE launch of a kernel made for this
+ *  shape (a group of lanes and a match table per row, one listed candidate per lane: csrc/hip/myers_rerank.hip); every other row is
+ *  an ordinary 1 x k engine call of its own.  One call may mix both; the `rerank` knob at 0 sends every row down the second route.
+ *  szs_rocm_last_call_profile reports the sums over the call: pairs (non-empty slots), cells, kernel time, launches, wall time.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_rerank(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                           sz_sequence_t const *candidates, sz_size_t const *indices, sz_size_t k, void *scores,
+                                           sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_rerank_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                   sz_sequence_u32tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                   void *scores, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_rerank_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                   sz_sequence_u64tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                   void *scores, sz_size_t row_stride, char const **error_message);
 
 /**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine
@@ -279,6 +316,7 @@ SZ_API_RUNTIME sz_status_t szs_rocm_node_scores_u64tape(szs_rocm_node_engine_t e
  *  few are beyond 16 - the tiny-token launch of hip/myers_tiny.hip | 2: the same, and blocks full of longer strings are scored there
  *  too, slowly, instead of refused (testing); automatic: batches of tiny tokens on both sides),
  *  "top_k_tile" (n: the most candidates per scored tile of a top-k call),
+ *  "rerank" (0: every row of a rerank call as an engine call of its own; automatic: qualifying rows in one launch of hip/myers_rerank.hip),
  *  "queues" (see below), "roctx" (1: the host phases of every call - plan, decide, enqueue, wait - as roctx ranges for a
  *  `rocprofv3 --marker-trace` timeline; the marker library is looked up at run time, never linked),
  *  "cpu_requests" (strict | gpu: serve capability

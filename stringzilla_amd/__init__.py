@@ -353,6 +353,66 @@ class _Engine:
         host = both[:, :rows].cpu().numpy()
         return host[0].view(np.uint64), host[1].view(self._dtype)
 
+    def rerank(self, queries, candidates, indices, device: Optional[DeviceScope] = None, out=None):
+        """Exact scores of the candidates `indices` lists per query (`szs_rocm_rerank_*`): `scores[q, r]` is the score of
+        `queries[q]` and `candidates[indices[q, r]]`, the cell the matrix call would hold there.  `indices` is a `(rows, k)` matrix
+        of 8-byte cells with contiguous rows - a NumPy array or a torch tensor, host or device - such as the one `top_k` or
+        `Fingerprints.top_k` returns; 2**64 - 1 marks an empty slot (score 0), any other index beyond the candidates is refused.
+        `candidates` None: the indices refer to `queries`.  Returns an engine-dtype `(rows, k)` NumPy matrix, or fills `out` (a
+        NumPy array or torch tensor of 8-byte cells that shares the row stride of `indices`)."""
+        import torch
+
+        def cells_of(matrix, name, shape_wanted):  # -> (pointer, row stride in cells, shape)
+            if isinstance(matrix, np.ndarray):
+                shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
+                pointer, whole = matrix.ctypes.data, all(s % 8 == 0 for s in matrix.strides)
+            elif type(matrix).__module__.partition(".")[0] == "torch" and hasattr(matrix, "data_ptr"):
+                shape, itemsize, strides, pointer, whole = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr(), True
+                if matrix.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
+                    torch.cuda.current_stream(matrix.device).synchronize()
+            else:
+                raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(matrix).__name__}")
+            if len(shape) != 2 or shape[1] < 1 or (shape_wanted is not None and shape != shape_wanted) or itemsize != 8 or not whole or (
+                    shape[1] > 1 and strides[1] != 1) or (shape[0] > 1 and strides[0] < shape[1]):
+                raise ValueError(f"`{name}` must be a (rows, k) matrix of 8-byte cells with contiguous rows, k at least 1")
+            return pointer, strides[0] if shape[0] > 1 else shape[1], shape
+
+        queries = _as_strs(queries)
+        candidates = None if candidates is None else _as_strs(candidates)
+        indices_pointer, stride, (rows, k) = cells_of(indices, "indices", None)
+        if rows != len(queries):
+            raise ValueError(f"`indices` must have one row per query: {rows} rows, {len(queries)} queries")
+        if out is not None:
+            scores_pointer, scores_stride, _ = cells_of(out, "out", (rows, k))
+            if scores_stride != stride:
+                raise ValueError("`out` and `indices` must share one row stride")
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        for matrix, name in ((indices, "indices"), (out, "out")):  # a device tensor goes to the kernel as a raw pointer
+            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:
+                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
+        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
+            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        if out is None:
+            if stride == k:
+                results = torch.empty((max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+            else:  # the scores share the stride of the indices: a host matrix as wide as theirs
+                results = np.zeros((max(rows, 1), stride), dtype=np.int64)
+            scores_pointer = results.data_ptr() if stride == k else results.ctypes.data
+
+        error = ctypes.c_char_p()
+        call = lib.szs_rocm_rerank_u64tape if queries.wide_offsets else lib.szs_rocm_rerank_u32tape
+        q_tape = queries._tape(gpu_device)
+        c_tape = None if candidates is None else candidates._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
+                      indices_pointer, k, scores_pointer, stride, ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        host = results[:rows].cpu().numpy() if stride == k else results[:rows, :k]
+        return host.view(self._dtype)
+
     def __del__(self):
         handle = getattr(self, "handle", None)
         if handle and self._free is not None:

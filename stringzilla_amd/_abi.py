@@ -82,6 +82,7 @@ _SCORE_INIT = (c_int, [c_void_p, c_void_p, c_int8, c_int8, c_void_p, c_int, ENGI
 _CALL = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 _FP_CALL = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ERR])
 _TOP_K = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ERR])
+_RERANK = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ERR])
 
 SIGNATURES = {
     "szs_version_major": (c_int, []), "szs_version_minor": (c_int, []), "szs_version_patch": (c_int, []),
@@ -131,6 +132,7 @@ SIGNATURES = {
     "szs_rocm_node_scores_u32tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_node_scores_u64tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_top_k": _TOP_K, "szs_rocm_top_k_u32tape": _TOP_K, "szs_rocm_top_k_u64tape": _TOP_K,
+    "szs_rocm_rerank": _RERANK, "szs_rocm_rerank_u32tape": _RERANK, "szs_rocm_rerank_u64tape": _RERANK,
     "szs_rocm_fingerprint_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t,
                                              c_void_p, c_size_t, ERR]),
     "szs_rocm_fingerprint_top_k": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t,
@@ -176,7 +178,7 @@ _KNOBS = {"tier": "SZS_ROCM_TIER", "swap": "SZS_ROCM_SWAP", "packed": "SZS_ROCM_
           "team": "SZS_ROCM_TEAM", "queues": "SZS_ROCM_QUEUES", "roctx": "SZS_ROCM_ROCTX",
           "queue": "SZS_ROCM_QUEUE", "queue_words": "SZS_ROCM_QUEUE_WORDS", "queue_rounds": "SZS_ROCM_QUEUE_ROUNDS",
           "queue_priority": "SZS_ROCM_QUEUE_PRIORITY", "fused": "SZS_ROCM_FUSED", "tiny": "SZS_ROCM_TINY",
-          "top_k_tile": "SZS_ROCM_TOP_K_TILE"}
+          "top_k_tile": "SZS_ROCM_TOP_K_TILE", "rerank": "SZS_ROCM_RERANK"}
 _knob_values = {name: os.environ.get(variable) for name, variable in _KNOBS.items()}  # what the library read when it was loaded
 
 

@@ -265,6 +265,37 @@ int szs_hip_fingerprint_matches_u64(uint32_t const *queries, uint64_t queries_st
                                     uint64_t candidates_stride, uint32_t columns, uint32_t dimensions, uint64_t *cells,
                                     uint64_t cells_stride, void *stream);
 
+/**
+ *  Rerank (hip/myers_rerank.hip; host/rerank.c): unit-cost byte Levenshtein distances of LISTED pairs -
+ *  scores[row * scores_stride + r] = distance(query first_query + row, candidate indices[row * indices_stride + r]) for r < k and
+ *  every `row` of `rows[0 .. rows_count)`.  A side is a tape (`offsets` of 4 or 8 bytes, `base` the address of its bytes) or, with
+ *  `refs`, an array of (address, length) in index order (callback sequences).  A group of `lanes` = 16 / 32 / 64 lanes serves one
+ *  row - its own Peq table in LDS, one listed candidate per lane, rows of more than 64 candidates in chunks of 64 - and a
+ *  one-wavefront workgroup holds 64 / lanes rows at the width of its longest query, so `rows` should arrive by DESCENDING query
+ *  length.  Every query of `rows` has at most 256 bytes (`widest` = the most 32-bit words any of them needs, 1 ... 8: sizes the
+ *  dynamic LDS); a longer one is not scored and sets `flags[SZS_RERANK_FLAG_UNFIT]`.  An index of ~0 is an empty
+ *  slot: score 0, no string touched.  Any other index >= the candidates' count is never used to address anything and sets
+ *  `flags[SZS_RERANK_FLAG_INDEX]`; offsets that descend or a string of 4 GiB and more set `flags[SZS_RERANK_FLAG_TAPE]`.  `flags`:
+ *  SZS_RERANK_FLAGS words of pinned host memory, zeroed by the caller, one per kind of failure - every store is the same 1.  `counters` (three qwords of device memory, zeroed by the caller): [0] += scored pairs, [1] += their cells, [2] += their bytes.
+ */
+typedef struct szs_rerank_side_t {
+    void const *offsets;          /* tapes: count + 1 entries */
+    uint64_t base;                /* tapes: address of the bytes */
+    szs_string_ref_t const *refs; /* sequences: string i is refs[i].length bytes at refs[i].address; NULL: a tape */
+    uint64_t count;
+    uint32_t wide;                /* tapes: 0 - 32-bit offsets, 1 - 64-bit */
+} szs_rerank_side_t;
+#define SZS_RERANK_LONGEST_QUERY 256u
+#define SZS_RERANK_FLAG_INDEX 0 /* the words of `flags`: one per kind of failure, so lanes that fail differently never overwrite each other */
+#define SZS_RERANK_FLAG_TAPE 1
+#define SZS_RERANK_FLAG_UNFIT 2
+#define SZS_RERANK_FLAGS 3
+unsigned szs_hip_rerank_lanes(uint64_t k);
+int szs_hip_levenshtein_rerank(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,
+                               uint32_t const *rows, uint32_t rows_count, uint64_t const *indices, uint64_t indices_stride, uint64_t k,
+                               uint64_t *scores, uint64_t scores_stride, unsigned widest, uint32_t *flags, unsigned long long *counters,
+                               void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {
@@ -298,6 +329,8 @@ enum {
     szs_knob_tiny_k,        /* -1 automatic (tiny tokens on both sides) | 0 never | 1 every unit-cost byte call of strings up to 255 bytes, few
                                of them beyond 16: the tiny-token launch of hip/myers_tiny.hip | 2 (testing): dense batches are scored there too */
     szs_knob_top_k_tile_k,  /* -1 automatic | n: the most candidates per scored tile of a top-k call (host/top_k.c) */
+    szs_knob_rerank_k,      /* -1 automatic (rows of a unit-cost byte engine whose query has at most 256 bytes: hip/myers_rerank.hip) |
+                               0: every row of a rerank call as an engine call of its own (host/rerank.c) */
     szs_knob_count_k
 };
 int szs_tuning_get(int knob);

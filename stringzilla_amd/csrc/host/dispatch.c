@@ -276,6 +276,9 @@ static void release_device_state(szs_engine_s *engine) {
     szs_buffer_release(&engine->device_top_k_scratch);
     szs_buffer_release(&engine->device_top_k_lists);
     szs_buffer_release(&engine->device_top_k_out);
+    szs_buffer_release(&engine->pinned_rerank);
+    szs_buffer_release(&engine->device_rerank);
+    szs_buffer_release(&engine->device_rerank_staged);
     szs_tiny_forget(&engine->tiny[0]), szs_tiny_forget(&engine->tiny[1]), engine->narrow_zeroed = NULL;
     engine->fused_zeroed = NULL;
     if (engine->events_device >= 0) {
@@ -312,6 +315,8 @@ void szs_engine_release(szs_engine_s *engine) {
     }
     szs_buffer_release(&engine->host_lengths);
     szs_buffer_release(&engine->host_scratch);
+    szs_buffer_release(&engine->host_rerank_offsets[0]), szs_buffer_release(&engine->host_rerank_offsets[1]);
+    szs_buffer_release(&engine->host_rerank);
     free(engine->remembered);
     engine->remembered = NULL;
 }

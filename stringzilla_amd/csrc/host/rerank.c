@@ -1,0 +1,463 @@
+/*
+ *  rerank.c - exact scores of LISTED candidates per query (szs_rocm_rerank*, include/stringzillas/stringzillas_rocm.h; DESIGN.md
+ *  section 4.8): scores[q][r] = score(queries[q], candidates[indices[q][r]]), the cell the matrix call would put there.
+ *
+ *  Two routes inside one call, chosen per row:
+ *    - the KERNEL route (hip/myers_rerank.hip): rows of a unit-cost byte Levenshtein engine whose query has at most 256 bytes.  All
+ *      such rows of a block go into one launch, dealt by descending query length; the kernel reads the indices and writes the scores
+ *      where they are when the device can reach them, else through a dense copy of the block;
+ *    - the ROW route: every other row - and every row with the `rerank` knob at 0 - is one ordinary engine call
+ *      (szs_engine_cross) of 1 x k' over a gathered sequence of the row's non-empty indices, scattered into the row on the host.
+ *  Indices the host can read are validated before anything is launched; indices only the device can read are checked by the kernel
+ *  (`index < count` before every use, a flag in pinned memory) - or, for the rows of the row route, downloaded and validated first.
+ *
+ *  szs_engine_rerank checks the arguments, lays out the scratch (rerank_layout), prepares the sides and walks the blocks; per block:
+ *  rerank_deal_rows (which rows the kernel takes, longest query first), rerank_kernel_rows (staging, the launch, the scores home),
+ *  rerank_row (the row route).  The two routes write disjoint rows of `scores`, so neither depends on running before the other.
+ */
+#include "szs_internal.h"
+
+#include <string.h>
+#include <time.h>
+
+#define SZS_RERANK_STAGE_BYTES ((size_t)128 << 20) /* a block's dense copy of indices or scores the device cannot reach */
+#define SZS_RERANK_MOST_ROWS ((size_t)1 << 20)     /* rows of a block: bounds the kernel's row list */
+#define SZS_RERANK_EMPTY (~(uint64_t)0)            /* SZ_SIZE_MAX: the empty slot top-k emits */
+
+static double now_milliseconds(void) {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
+/* ---- gathered sequences: strings picks[0 .. count) of a side, for the row route ------------------------------------------- */
+
+typedef struct {
+    sz_sequence_t sequence; /* first member: the handle of the wrapper is the wrapper itself */
+    szs_input_t const *base;
+    void const *offsets;    /* of a tape, where the host can read them */
+    uint64_t const *picks;
+} szs_gathered_sequence_t;
+
+static uint64_t tape_offset(szs_input_t const *input, void const *offsets, size_t i) {
+    return input->kind == szs_input_u32tape_k ? ((uint32_t const *)offsets)[i] : ((uint64_t const *)offsets)[i];
+}
+static sz_cptr_t gathered_start(void const *handle, sz_sorted_idx_t i) {
+    szs_gathered_sequence_t const *gathered = (szs_gathered_sequence_t const *)handle;
+    size_t const at = (size_t)gathered->picks[i];
+    if (gathered->base->kind == szs_input_sequence_k) return gathered->base->sequence->get_start(gathered->base->sequence->handle, at);
+    return gathered->base->data + tape_offset(gathered->base, gathered->offsets, at);
+}
+static sz_size_t gathered_length(void const *handle, sz_sorted_idx_t i) {
+    szs_gathered_sequence_t const *gathered = (szs_gathered_sequence_t const *)handle;
+    size_t const at = (size_t)gathered->picks[i];
+    if (gathered->base->kind == szs_input_sequence_k) return gathered->base->sequence->get_length(gathered->base->sequence->handle, at);
+    uint64_t const from = tape_offset(gathered->base, gathered->offsets, at), to = tape_offset(gathered->base, gathered->offsets, at + 1);
+    return to >= from ? to - from : SZS_RERANK_EMPTY; /* descending offsets: a length no call accepts */
+}
+static szs_input_t gather_input(szs_input_t const *base, void const *offsets, uint64_t const *picks, size_t count,
+                                szs_gathered_sequence_t *wrapper) {
+    wrapper->base = base, wrapper->offsets = offsets, wrapper->picks = picks;
+    wrapper->sequence.handle = wrapper, wrapper->sequence.count = count;
+    wrapper->sequence.get_start = gathered_start, wrapper->sequence.get_length = gathered_length;
+    szs_input_t const input = {szs_input_sequence_k, count, NULL, NULL, &wrapper->sequence};
+    return input;
+}
+
+/** The offsets of a tape where the host can read them: as they are, or copied to the host - once per call. */
+static sz_status_t host_offsets_of(szs_input_t const *input, szs_buffer_t *copy, hipStream_t stream, void const **offsets,
+                                   char const **error_message) {
+    *offsets = input->offsets;
+    if (input->kind == szs_input_sequence_k) return sz_success_k;
+    if (!input->offsets) return szs_report(sz_status_unknown_k, error_message, "Tape offsets must not be null");
+    if (szs_classify_pointer(input->offsets).host_readable) return sz_success_k;
+    size_t const bytes = (input->count + 1) * (input->kind == szs_input_u32tape_k ? 4 : 8);
+    sz_status_t const status = szs_buffer_reserve(copy, szs_memory_host_k, 0, bytes, error_message);
+    if (status != sz_success_k) return status;
+    hipError_t error = hipMemcpyAsync(copy->pointer, input->offsets, bytes, hipMemcpyDeviceToHost, stream);
+    if (error == hipSuccess) error = hipStreamSynchronize(stream);
+    if (error != hipSuccess) return szs_report_hip(error, error_message);
+    *offsets = copy->pointer;
+    return sz_success_k;
+}
+
+static size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+/** A side does not need refs when it is a tape whose offsets the device reads itself. */
+static int side_needs_refs(szs_input_t const *input) {
+    return input->kind == szs_input_sequence_k || !szs_classify_pointer(input->offsets).device_accessible;
+}
+
+/**
+ *  One side as the kernel reads it: the tape itself, or refs in index order built on the host and uploaded.  `*usable` 0: the kernel
+ *  cannot reach the side's strings (or its offsets are malformed) - every row then takes the row route, which reports what is wrong.
+ */
+static sz_status_t kernel_side(szs_input_t const *input, void const *offsets, int needs_refs, uint64_t *addresses, uint32_t *lengths,
+                               szs_string_ref_t *pinned_refs, szs_string_ref_t *device_refs, hipStream_t stream, szs_rerank_side_t *side,
+                               int *usable, char const **error_message) {
+    memset(side, 0, sizeof(*side));
+    side->count = input->count, *usable = 1;
+    if (!needs_refs) {
+        side->offsets = input->offsets, side->base = (uint64_t)(uintptr_t)input->data, side->wide = input->kind == szs_input_u64tape_k;
+        uint64_t const bytes = tape_offset(input, offsets, input->count) - tape_offset(input, offsets, 0);
+        *usable = !bytes || szs_classify_pointer(input->data).device_accessible;
+        return sz_success_k;
+    }
+    char const *ignored = NULL;
+    uint64_t bytes = 0;
+    if (szs_gather_strings(input, offsets, addresses, lengths, &bytes, NULL, &ignored) != sz_success_k) {
+        *usable = 0;
+        return sz_success_k;
+    }
+    for (size_t i = 0; i < input->count; ++i)
+        pinned_refs[i].address = addresses[i], pinned_refs[i].length = lengths[i], pinned_refs[i].index = (uint32_t)i;
+    side->refs = device_refs;
+    if (!input->count) return sz_success_k;
+    hipError_t const error = hipMemcpyAsync(device_refs, pinned_refs, input->count * sizeof(szs_string_ref_t), hipMemcpyHostToDevice, stream);
+    return error == hipSuccess ? sz_success_k : szs_report_hip(error, error_message);
+}
+
+static void add_profile(szs_rocm_call_profile_t *total, szs_rocm_call_profile_t const *part) {
+    total->kernel_milliseconds += part->kernel_milliseconds, total->cells += part->cells, total->pairs += part->pairs;
+    total->algorithmic_bytes += part->algorithmic_bytes, total->unique_bytes += part->unique_bytes, total->launches += part->launches;
+    if (part->longest_query > total->longest_query) total->longest_query = part->longest_query;
+    if (part->longest_candidate > total->longest_candidate) total->longest_candidate = part->longest_candidate;
+}
+
+static int index_is_bad(uint64_t index, size_t count) { return index != SZS_RERANK_EMPTY && index >= count; }
+
+/* ---- scratch layouts ------------------------------------------------------------------------------------------------------ */
+
+/** Byte offsets of every part of the engine's rerank buffers: computed in ONE place, each part behind the one before it. */
+typedef struct {
+    /* engine->host_rerank */
+    size_t host_query_lengths;    /* u32 x queries */
+    size_t host_addresses;        /* u64 x gathered strings of the larger side */
+    size_t host_gathered_lengths; /* u32 x the same */
+    size_t host_indices;          /* u64 x block x k: a block of indices only the device can read (else empty) */
+    size_t host_picks;            /* u64 x k: a row's non-empty indices */
+    size_t host_bytes;
+    /* engine->pinned_rerank */
+    size_t pinned_flags;   /* u32 x SZS_RERANK_FLAGS: the kernel's */
+    size_t pinned_landed;  /* u64 x 3: the kernel's counters, downloaded */
+    size_t pinned_cells;   /* u64 x k: a row's scores as the engine call leaves them */
+    size_t pinned_image;   /* u64 x k: the row as it is written */
+    size_t pinned_rows;    /* u32 x block: the kernel's rows */
+    size_t pinned_refs;    /* refs of the queries, then of the candidates */
+    size_t pinned_bytes;
+    /* engine->device_rerank */
+    size_t device_counters; /* u64 x 3 */
+    size_t device_rows;     /* u32 x block */
+    size_t device_refs;     /* as pinned_refs */
+    size_t device_bytes;
+} szs_rerank_layout_t;
+
+static size_t layout_part(size_t *end, size_t bytes) {
+    size_t const at = *end;
+    *end = at + align16(bytes);
+    return at;
+}
+
+static szs_rerank_layout_t rerank_layout(size_t q_count, size_t gathered, size_t block, size_t k, int indices_on_host, size_t refs_total) {
+    szs_rerank_layout_t layout;
+    size_t end = 0;
+    layout.host_query_lengths = layout_part(&end, q_count * sizeof(uint32_t));
+    layout.host_addresses = layout_part(&end, gathered * sizeof(uint64_t));
+    layout.host_gathered_lengths = layout_part(&end, gathered * sizeof(uint32_t));
+    layout.host_indices = layout_part(&end, indices_on_host ? 0 : block * k * sizeof(uint64_t));
+    layout.host_picks = layout_part(&end, k * sizeof(uint64_t));
+    layout.host_bytes = end, end = 0;
+    layout.pinned_flags = layout_part(&end, SZS_RERANK_FLAGS * sizeof(uint32_t));
+    layout.pinned_landed = layout_part(&end, 3 * sizeof(uint64_t));
+    layout.pinned_cells = layout_part(&end, k * sizeof(uint64_t));
+    layout.pinned_image = layout_part(&end, k * sizeof(uint64_t));
+    layout.pinned_rows = layout_part(&end, block * sizeof(uint32_t));
+    layout.pinned_refs = layout_part(&end, refs_total * sizeof(szs_string_ref_t));
+    layout.pinned_bytes = end, end = 0;
+    layout.device_counters = layout_part(&end, 3 * sizeof(uint64_t));
+    layout.device_rows = layout_part(&end, block * sizeof(uint32_t));
+    layout.device_refs = layout_part(&end, refs_total * sizeof(szs_string_ref_t));
+    layout.device_bytes = end;
+    return layout;
+}
+
+/* ---- the call ------------------------------------------------------------------------------------------------------------ */
+
+/** What the parts of one call share. */
+typedef struct {
+    szs_engine_s *engine;
+    szs_scope_s *scope;
+    hipStream_t stream;
+    szs_input_t const *queries, *pool; /* pool: the candidates, or the queries in the self form */
+    void const *query_offsets, *pool_offsets;
+    size_t k, row_stride, block;
+    uint64_t const *indices;
+    uint64_t *scores;
+    int scores_on_host, stage_indices, stage_scores;
+    int kernel_route;
+    szs_rerank_side_t sides[2];
+    uint32_t *query_lengths; /* kernel_route: per query, ~0 where the kernel does not take it */
+    uint64_t *picks, *landed, *row_cells, *row_image;
+    uint32_t *flags, *order, *device_order;
+    unsigned long long *device_counters;
+    szs_rocm_call_profile_t total;
+    int engine_calls;
+} szs_rerank_call_t;
+
+static int row_takes_kernel(szs_rerank_call_t const *call, size_t query) {
+    return call->kernel_route && call->query_lengths[query] <= SZS_RERANK_LONGEST_QUERY;
+}
+
+/** The kernel's rows of block [q0, q0 + rows) into `order`, longest query first (a counting sort of the lengths 256 ... 0). */
+static size_t rerank_deal_rows(szs_rerank_call_t const *call, size_t q0, size_t rows, uint32_t *longest) {
+    *longest = 0;
+    if (!call->kernel_route) return 0;
+    uint32_t bins[SZS_RERANK_LONGEST_QUERY + 2];
+    size_t kernel_rows = 0;
+    memset(bins, 0, sizeof(bins));
+    for (size_t r = 0; r < rows; ++r)
+        if (row_takes_kernel(call, q0 + r)) ++bins[SZS_RERANK_LONGEST_QUERY - call->query_lengths[q0 + r] + 1], ++kernel_rows;
+    for (size_t b = 1; b < SZS_RERANK_LONGEST_QUERY + 2; ++b) bins[b] += bins[b - 1];
+    for (size_t r = 0; r < rows; ++r) {
+        if (!row_takes_kernel(call, q0 + r)) continue;
+        uint32_t const length = call->query_lengths[q0 + r];
+        call->order[bins[SZS_RERANK_LONGEST_QUERY - length]++] = (uint32_t)r;
+        if (length > *longest) *longest = length;
+    }
+    return kernel_rows;
+}
+
+/**
+ *  The kernel route of one block: stages what the device cannot reach, launches once, brings the scores home, reads the flags.
+ *  Staged scores go home by RUNS of consecutive kernel rows - one 2-D copy when the kernel took the whole block - so the rows of
+ *  the row route are never written from here.
+ */
+static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t rows, size_t kernel_rows, uint32_t longest,
+                                      hipError_t *hip_error, char const **error_message) {
+    szs_engine_s *const engine = call->engine;
+    hipStream_t const stream = call->stream;
+    size_t const k = call->k, row_stride = call->row_stride, row_bytes = k * sizeof(uint64_t);
+    uint64_t *const staged = (uint64_t *)engine->device_rerank_staged.pointer;
+    uint64_t const *kernel_indices = call->indices + q0 * row_stride;
+    uint64_t *kernel_scores = call->scores + q0 * row_stride;
+    size_t kernel_indices_stride = row_stride, kernel_scores_stride = row_stride;
+    unsigned const widest = longest ? (longest + 31) / 32 : 1;
+    hipError_t error = hipSuccess;
+    if (call->stage_indices) {
+        error = hipMemcpy2DAsync(staged, row_bytes, call->indices + q0 * row_stride, row_stride * sizeof(uint64_t), row_bytes, rows,
+                                 hipMemcpyHostToDevice, stream);
+        kernel_indices = staged, kernel_indices_stride = k;
+    }
+    if (call->stage_scores) kernel_scores = staged + (call->stage_indices ? call->block * k : 0), kernel_scores_stride = k;
+    memset(call->flags, 0, SZS_RERANK_FLAGS * sizeof(uint32_t));
+    if (error == hipSuccess) error = hipMemsetAsync(call->device_counters, 0, 3 * sizeof(uint64_t), stream);
+    if (error == hipSuccess)
+        error = hipMemcpyAsync(call->device_order, call->order, kernel_rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+    if (error == hipSuccess) error = hipEventRecord(engine->event_start, stream);
+    if (error == hipSuccess)
+        error = (hipError_t)szs_hip_levenshtein_rerank(&call->sides[0], &call->sides[1], q0, call->device_order, (uint32_t)kernel_rows,
+                                                       kernel_indices, kernel_indices_stride, k, kernel_scores, kernel_scores_stride, widest,
+                                                       call->flags, call->device_counters, stream);
+    if (error == hipSuccess) error = hipEventRecord(engine->event_stop, stream);
+    if (error == hipSuccess) error = hipMemcpyAsync(call->landed, call->device_counters, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+    for (size_t r = 0; r < rows && error == hipSuccess && call->stage_scores;) {
+        if (!row_takes_kernel(call, q0 + r)) {
+            ++r;
+            continue;
+        }
+        size_t run = r + 1;
+        while (run < rows && row_takes_kernel(call, q0 + run)) ++run;
+        error = hipMemcpy2DAsync(call->scores + (q0 + r) * row_stride, row_stride * sizeof(uint64_t), kernel_scores + r * k, row_bytes, row_bytes,
+                                 run - r, hipMemcpyDeviceToHost, stream);
+        r = run;
+    }
+    hipError_t const drained = hipStreamSynchronize(stream);
+    if (error == hipSuccess) error = drained;
+    if (error != hipSuccess) {
+        *hip_error = error;
+        return sz_success_k;
+    }
+    if (call->flags[SZS_RERANK_FLAG_UNFIT]) return szs_report(sz_status_unknown_k, error_message, "A query beyond the rerank kernel's width");
+    if (call->flags[SZS_RERANK_FLAG_TAPE]) return szs_report(sz_unexpected_dimensions_k, error_message, "Tape offsets must ascend");
+    if (call->flags[SZS_RERANK_FLAG_INDEX]) return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
+    float milliseconds = 0;
+    if (hipEventElapsedTime(&milliseconds, engine->event_start, engine->event_stop) != hipSuccess) (void)hipGetLastError();
+    szs_rocm_call_profile_t *const total = &call->total;
+    total->kernel_milliseconds += milliseconds, total->launches += 1, total->pairs += call->landed[0], total->cells += call->landed[1];
+    total->algorithmic_bytes += call->landed[2] + call->landed[0] * (2 * 4 + 8);
+    if (longest > total->longest_query) total->longest_query = longest;
+    return sz_success_k;
+}
+
+/** The row route of one row: one engine call of 1 x k' over the row's non-empty indices, scattered into the row. */
+static sz_status_t rerank_row(szs_rerank_call_t *call, size_t query, uint64_t const *row_indices, hipError_t *hip_error,
+                              char const **error_message) {
+    size_t const k = call->k;
+    size_t listed = 0;
+    for (size_t i = 0; i < k; ++i)
+        if (row_indices[i] != SZS_RERANK_EMPTY) call->picks[listed++] = row_indices[i];
+    if (listed) {
+        uint64_t const query_pick = query;
+        szs_gathered_sequence_t query_wrapper, candidate_wrapper;
+        szs_input_t const one = gather_input(call->queries, call->query_offsets, &query_pick, 1, &query_wrapper);
+        szs_input_t const few = gather_input(call->pool, call->pool_offsets, call->picks, listed, &candidate_wrapper);
+        sz_status_t const status = szs_engine_cross(call->engine, call->scope, &one, &few, call->row_cells, listed, error_message); /* synchronous */
+        if (status != sz_success_k) return status;
+        add_profile(&call->total, &call->engine->last_profile), ++call->engine_calls;
+    }
+    for (size_t i = 0, next = 0; i < k; ++i) call->row_image[i] = row_indices[i] != SZS_RERANK_EMPTY ? call->row_cells[next++] : 0;
+    uint64_t *const row_scores = call->scores + query * call->row_stride;
+    if (call->scores_on_host) memcpy(row_scores, call->row_image, k * sizeof(uint64_t));
+    else { /* (the image is free again once this copy has run: nothing writes it before the next synchronisation) */
+        hipError_t error = hipMemcpyAsync(row_scores, call->row_image, k * sizeof(uint64_t), hipMemcpyHostToDevice, call->stream);
+        if (error == hipSuccess) error = hipStreamSynchronize(call->stream);
+        *hip_error = error;
+    }
+    return sz_success_k;
+}
+
+sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                              size_t const *indices, size_t k, void *scores, size_t row_stride, char const **error_message) {
+    double const started = now_milliseconds();
+    if (k < 1 || row_stride < k) return szs_report(sz_unexpected_dimensions_k, error_message, "k must be at least 1 and row_stride at least k");
+    if (!engine || engine->magic != SZS_ENGINE_MAGIC || (unsigned)engine->family > szs_family_smith_waterman_k)
+        return szs_report(sz_status_unknown_k, error_message, "Engine must be an initialized similarity engine");
+    if (!queries) return szs_report(sz_status_unknown_k, error_message, "Queries must not be null");
+    if (!queries->count) return szs_report(sz_success_k, error_message, NULL);
+    if (!indices) return szs_report(sz_status_unknown_k, error_message, "Indices must not be null");
+    if (!scores) return szs_report(sz_status_unknown_k, error_message, "Scores must not be null");
+    if (k > (~(size_t)0 >> 4) / sizeof(uint64_t)) return szs_report(sz_overflow_risk_k, error_message, NULL);
+
+    int device = 0;
+    hipStream_t stream = NULL;
+    sz_status_t status = szs_scope_bind_gpu(scope, &device, &stream, error_message);
+    if (status != sz_success_k) return status;
+    szs_engine_follow_device(engine, device);
+    if (engine->events_device != device) {
+        hipError_t error = hipEventCreate(&engine->event_start);
+        if (error == hipSuccess) error = hipEventCreate(&engine->event_stop);
+        if (error != hipSuccess) return szs_report_hip(error, error_message);
+        engine->events_device = device;
+    }
+
+    szs_rerank_call_t call;
+    memset(&call, 0, sizeof(call));
+    call.engine = engine, call.scope = scope, call.stream = stream, call.queries = queries;
+    call.pool = candidates ? candidates : queries; /* the self form: the indices refer to the queries */
+    call.k = k, call.row_stride = row_stride, call.indices = (uint64_t const *)indices, call.scores = (uint64_t *)scores;
+    size_t const q_count = queries->count, c_count = call.pool->count;
+    szs_pointer_traits_t const index_traits = szs_classify_pointer(indices), score_traits = szs_classify_pointer(scores);
+    call.scores_on_host = score_traits.host_readable;
+
+    /* indices the host can read: validated before anything is launched */
+    if (index_traits.host_readable)
+        for (size_t q = 0; q < q_count; ++q)
+            for (size_t r = 0; r < k; ++r)
+                if (index_is_bad(call.indices[q * row_stride + r], c_count))
+                    return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
+
+    status = host_offsets_of(queries, &engine->host_rerank_offsets[0], stream, &call.query_offsets, error_message);
+    if (status == sz_success_k && candidates)
+        status = host_offsets_of(candidates, &engine->host_rerank_offsets[1], stream, &call.pool_offsets, error_message);
+    if (status != sz_success_k) return status;
+    if (!candidates) call.pool_offsets = call.query_offsets;
+
+    /* blocks of rows: the kernel's row list and - where the device cannot reach the caller's arrays - their dense copies in budget */
+    call.stage_indices = !index_traits.device_accessible, call.stage_scores = !score_traits.device_accessible;
+    size_t block = q_count < SZS_RERANK_MOST_ROWS ? q_count : SZS_RERANK_MOST_ROWS;
+    if ((call.stage_indices || call.stage_scores || !index_traits.host_readable) && block > SZS_RERANK_STAGE_BYTES / (k * sizeof(uint64_t)))
+        block = SZS_RERANK_STAGE_BYTES / (k * sizeof(uint64_t));
+    if (block < 1) block = 1;
+    call.block = block;
+
+    call.kernel_route = szs_tuning_get(szs_knob_rerank_k) != 0 && engine->family == szs_family_levenshtein_k && engine->is_unit_cost;
+    int const refs_needed[2] = {call.kernel_route && side_needs_refs(queries), call.kernel_route && candidates && side_needs_refs(candidates)};
+    size_t const refs_count[2] = {refs_needed[0] ? q_count : 0, refs_needed[1] ? c_count : 0};
+    size_t const gathered = refs_count[0] > refs_count[1] ? refs_count[0] : refs_count[1];
+    szs_rerank_layout_t const layout = rerank_layout(q_count, gathered, block, k, index_traits.host_readable, refs_count[0] + refs_count[1]);
+
+    status = szs_buffer_reserve(&engine->host_rerank, szs_memory_host_k, 0, layout.host_bytes, error_message);
+    if (status == sz_success_k) status = szs_buffer_reserve(&engine->pinned_rerank, szs_memory_pinned_k, device, layout.pinned_bytes, error_message);
+    if (status == sz_success_k && call.kernel_route)
+        status = szs_buffer_reserve(&engine->device_rerank, szs_memory_device_k, device, layout.device_bytes, error_message);
+    if (status == sz_success_k && call.kernel_route && (call.stage_indices || call.stage_scores))
+        status = szs_buffer_reserve(&engine->device_rerank_staged, szs_memory_device_k, device,
+                                    ((size_t)call.stage_indices + (size_t)call.stage_scores) * block * k * sizeof(uint64_t), error_message);
+    if (status != sz_success_k) return status;
+    char *const host = (char *)engine->host_rerank.pointer, *const pinned = (char *)engine->pinned_rerank.pointer;
+    char *const remote = (char *)engine->device_rerank.pointer;
+    uint64_t *const downloaded = (uint64_t *)(host + layout.host_indices);
+    call.query_lengths = (uint32_t *)(host + layout.host_query_lengths), call.picks = (uint64_t *)(host + layout.host_picks);
+    call.flags = (uint32_t *)(pinned + layout.pinned_flags), call.landed = (uint64_t *)(pinned + layout.pinned_landed);
+    call.row_cells = (uint64_t *)(pinned + layout.pinned_cells), call.row_image = (uint64_t *)(pinned + layout.pinned_image);
+    call.order = (uint32_t *)(pinned + layout.pinned_rows);
+
+    if (call.kernel_route) {
+        call.device_counters = (unsigned long long *)(remote + layout.device_counters);
+        call.device_order = (uint32_t *)(remote + layout.device_rows);
+        szs_string_ref_t *const pinned_refs = (szs_string_ref_t *)(pinned + layout.pinned_refs);
+        szs_string_ref_t *const device_refs = (szs_string_ref_t *)(remote + layout.device_refs);
+        uint64_t *const addresses = (uint64_t *)(host + layout.host_addresses);
+        uint32_t *const lengths = (uint32_t *)(host + layout.host_gathered_lengths);
+        int usable = 0;
+        status = kernel_side(queries, call.query_offsets, refs_needed[0], addresses, lengths, pinned_refs, device_refs, stream, &call.sides[0],
+                             &usable, error_message);
+        if (status != sz_success_k) return status;
+        if (!usable) call.kernel_route = 0;
+        /* the lengths of the queries: which rows the kernel takes, and the order it takes them in */
+        for (size_t q = 0; q < q_count && call.kernel_route; ++q) {
+            if (refs_needed[0]) call.query_lengths[q] = lengths[q];
+            else {
+                uint64_t const from = tape_offset(queries, call.query_offsets, q), to = tape_offset(queries, call.query_offsets, q + 1);
+                call.query_lengths[q] = to >= from && to - from <= SZS_RERANK_LONGEST_QUERY ? (uint32_t)(to - from) : ~0u;
+            }
+        }
+        if (call.kernel_route && candidates) {
+            status = kernel_side(candidates, call.pool_offsets, refs_needed[1], addresses, lengths, pinned_refs + refs_count[0],
+                                 device_refs + refs_count[0], stream, &call.sides[1], &usable, error_message);
+            if (status != sz_success_k) return status;
+            if (!usable) call.kernel_route = 0;
+        }
+        else if (call.kernel_route)
+            call.sides[1] = call.sides[0];
+    }
+
+    hipError_t error = hipSuccess;
+    for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block) {
+        size_t const rows = q_count - q0 < block ? q_count - q0 : block;
+        uint32_t longest = 0;
+        size_t const kernel_rows = rerank_deal_rows(&call, q0, rows, &longest);
+
+        /* the rows of the row route need their indices on the host: downloaded and validated before anything is launched */
+        uint64_t const *host_indices = call.indices + q0 * row_stride;
+        size_t host_indices_stride = row_stride;
+        if (!index_traits.host_readable && kernel_rows < rows) {
+            error = hipMemcpy2DAsync(downloaded, k * sizeof(uint64_t), call.indices + q0 * row_stride, row_stride * sizeof(uint64_t),
+                                     k * sizeof(uint64_t), rows, hipMemcpyDeviceToHost, stream);
+            if (error == hipSuccess) error = hipStreamSynchronize(stream);
+            if (error != hipSuccess) break;
+            for (size_t i = 0; i < rows * k && status == sz_success_k; ++i)
+                if (index_is_bad(downloaded[i], c_count))
+                    status = szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
+            if (status != sz_success_k) break;
+            host_indices = downloaded, host_indices_stride = k;
+        }
+
+        if (kernel_rows) status = rerank_kernel_rows(&call, q0, rows, kernel_rows, longest, &error, error_message);
+        for (size_t r = 0; r < rows && kernel_rows < rows && status == sz_success_k && error == hipSuccess; ++r)
+            if (!row_takes_kernel(&call, q0 + r)) status = rerank_row(&call, q0 + r, host_indices + r * host_indices_stride, &error, error_message);
+    }
+    hipError_t const drained = hipStreamSynchronize(stream); /* synchronous, also when it fails */
+    if (status != sz_success_k) return status;
+    if (error == hipSuccess) error = drained;
+    if (error != hipSuccess) return szs_report_hip(error, error_message);
+    /* the profile of a rerank call: the last engine call's (none: blank), with the sums over the launch and every engine call */
+    if (!call.engine_calls) memset(&engine->last_profile, 0, sizeof(engine->last_profile));
+    szs_rocm_call_profile_t const *const total = &call.total;
+    engine->last_profile.kernel_milliseconds = total->kernel_milliseconds, engine->last_profile.cells = total->cells;
+    engine->last_profile.pairs = total->pairs, engine->last_profile.algorithmic_bytes = total->algorithmic_bytes;
+    engine->last_profile.unique_bytes = total->unique_bytes, engine->last_profile.launches = total->launches;
+    engine->last_profile.longest_query = total->longest_query, engine->last_profile.longest_candidate = total->longest_candidate;
+    engine->last_profile.host_milliseconds = now_milliseconds() - started;
+    return szs_report(sz_success_k, error_message, NULL);
+}

@@ -155,6 +155,13 @@ typedef struct szs_engine_s {
     szs_buffer_t device_top_k_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
     szs_buffer_t device_top_k_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
 
+    /* rerank calls (host/rerank.c) */
+    szs_buffer_t host_rerank_offsets[2]; /* host: tape offsets only the device can read - queries, candidates */
+    szs_buffer_t host_rerank;            /* host: query lengths, gathered strings, a block of indices only the device can read, a row's picks */
+    szs_buffer_t pinned_rerank;          /* pinned: the kernel's flag, its counters, a row's cells and image, the kernel's rows, refs of both sides */
+    szs_buffer_t device_rerank;          /* device: the counters, the kernel's rows, the refs */
+    szs_buffer_t device_rerank_staged;   /* device: dense indices, then scores, of a block whose arrays the device cannot reach */
+
     szs_rocm_call_profile_t last_profile;
 } szs_engine_s;
 
@@ -375,5 +382,11 @@ void szs_engine_follow_device(szs_engine_s *engine, int device);
 /** `candidates` NULL: self-search (each query against all queries but itself). */
 sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                              size_t k, size_t *indices, void *scores, size_t row_stride, char const **error_message);
+
+/* ---- rerank (rerank.c) -------------------------------------------------------------------------------------------------- */
+
+/** `candidates` NULL: the indices refer to the queries themselves (no index is excluded). */
+sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                              size_t const *indices, size_t k, void *scores, size_t row_stride, char const **error_message);
 
 #endif /* SZS_INTERNAL_H_ */
