@@ -7,7 +7,7 @@
  *    (/root/reference/include/stringzillas/types.cuh:280-298,482-534; bench/similarities.cuh:303-308).
  *  - szs_rocm_shard_rows        : longest-processing-time assignment of query rows to N GPUs;
  *    the reference has no multi-GPU path at all (one engine call = one device, stringzillas.h:137).
- *  - szs_rocm_plan_probe, szs_rocm_orientation_probe, szs_rocm_team_orientation_probe, szs_rocm_launch_order_probe,
+ *  - szs_rocm_rerank_probe, szs_rocm_plan_probe, szs_rocm_orientation_probe, szs_rocm_team_orientation_probe, szs_rocm_launch_order_probe,
  *    szs_rocm_queue_probe : expose
  *    the host planner - refs, tier and orientation, lanes per item, launch shapes and order - so that it is unit-tested
  *    without a GPU (tests/test_host_logic.py).
@@ -121,8 +121,12 @@ SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope
  *  unified or device memory, as may the strings' offsets.  The call runs on the scope's stream and is synchronous, also when it fails.
  *
  *  Rows of a unit-cost byte Levenshtein engine whose query has at most 256 bytes are scored by ONE launch of a kernel made for this
- *  shape (a group of lanes and a match table per row, one listed candidate per lane: csrc/hip/myers_rerank.hip); every other row is
- *  an ordinary 1 x k engine call of its own.  One call may mix both; the `rerank` knob at 0 sends every row down the second route.
+ *  shape (a group of lanes and a match table per row, one listed candidate per lane: csrc/hip/myers_rerank.hip); rows whose query
+ *  has more than 256 and at most 65,536 bytes - documents - by ONE launch of its twin that walks the query as strips of up to 256
+ *  rows (csrc/hip/myers_rerank_strips.hip); every other row is an ordinary 1 x k engine call of its own.  64 KiB is a design bound,
+ *  not a measured one: beyond it one lane's serial chain over the strips is the wrong tool and the engine's chained tiers for few
+ *  long pairs, which the engine call reaches, are built for such rows.  One call may mix all three; the `rerank` knob at 0 sends
+ *  every row down the last route, at 1 every row of more than 256 bytes.
  *  szs_rocm_last_call_profile reports the sums over the call: pairs (non-empty slots), cells, kernel time, launches, wall time.
  */
 SZ_API_RUNTIME sz_status_t szs_rocm_rerank(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
@@ -170,6 +174,20 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fingerprint_top_k(szs_fingerprints_t engine,
                                                       sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_size_t k,
                                                       sz_size_t *indices, sz_size_t *matches, sz_size_t row_stride,
                                                       char const **error_message);
+
+/**
+ *  The routing of a rerank call over queries of these lengths (bytes) with `k` slots per row, against a candidate side whose
+ *  longest string has `longest_candidate` bytes - no GPU involved, and the functions the call itself runs (csrc/host/rerank.c).
+ *  `unit_cost`: the engine is unit-cost Levenshtein; `runes`: it counts codepoints.  Outputs (all optional): routes[q] - 0 an engine
+ *  call of the row's own, 1 the kernel of csrc/hip/myers_rerank.hip, 2 the strips kernel of csrc/hip/myers_rerank_strips.hip;
+ *  strips[q] and strip_words[q] - how many strips the query is walked in and their width in 32-bit words (one strip of the query's
+ *  own width on route 1, zeros on route 0; rows that share a wavefront run at the shape of its longest query);
+ *  `*scratch_bytes` - the parked deltas the strips launch of these rows would allocate (0: no row takes it).  The `rerank` knob
+ *  applies as it does to the call.  k >= 1, else sz_unexpected_dimensions_k.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_rerank_probe(int unit_cost, int runes, sz_u32_t const *query_lengths, sz_size_t queries_count,
+                                                 sz_size_t k, sz_size_t longest_candidate, sz_u8_t *routes, sz_u32_t *strips,
+                                                 sz_u32_t *strip_words, sz_size_t *scratch_bytes);
 
 /**
  *  Runs the host planner on bare length arrays.  Outputs (all optional):
@@ -316,7 +334,9 @@ SZ_API_RUNTIME sz_status_t szs_rocm_node_scores_u64tape(szs_rocm_node_engine_t e
  *  few are beyond 16 - the tiny-token launch of hip/myers_tiny.hip | 2: the same, and blocks full of longer strings are scored there
  *  too, slowly, instead of refused (testing); automatic: batches of tiny tokens on both sides),
  *  "top_k_tile" (n: the most candidates per scored tile of a top-k call),
- *  "rerank" (0: every row of a rerank call as an engine call of its own; automatic: qualifying rows in one launch of hip/myers_rerank.hip),
+ *  "rerank" (0: every row of a rerank call as an engine call of its own | 1: rows whose query has at most 256 bytes in one launch of
+ *  hip/myers_rerank.hip, longer rows as engine calls; automatic: those, and rows whose query has at most 64 KiB in one launch of
+ *  hip/myers_rerank_strips.hip),
  *  "queues" (see below), "roctx" (1: the host phases of every call - plan, decide, enqueue, wait - as roctx ranges for a
  *  `rocprofv3 --marker-trace` timeline; the marker library is looked up at run time, never linked),
  *  "cpu_requests" (strict | gpu: serve capability

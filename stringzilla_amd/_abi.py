@@ -133,6 +133,7 @@ SIGNATURES = {
     "szs_rocm_node_scores_u64tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_top_k": _TOP_K, "szs_rocm_top_k_u32tape": _TOP_K, "szs_rocm_top_k_u64tape": _TOP_K,
     "szs_rocm_rerank": _RERANK, "szs_rocm_rerank_u32tape": _RERANK, "szs_rocm_rerank_u64tape": _RERANK,
+    "szs_rocm_rerank_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "szs_rocm_fingerprint_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t,
                                              c_void_p, c_size_t, ERR]),
     "szs_rocm_fingerprint_top_k": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t,
@@ -191,6 +192,23 @@ def tuning_set(knob: str, value=None):
         raise ValueError(f"unknown tuning knob {knob!r}")
     previous, _knob_values[name] = _knob_values[name], None if value is None else str(value)
     return previous
+
+
+def rerank_probe(query_lengths, k, longest_candidate, unit_cost=True, runes=False):
+    """`szs_rocm_rerank_probe`: how a rerank call would route queries of these byte lengths - no GPU involved.  Returns
+    (routes, strips, strip_words, scratch_bytes): per query 0 (an engine call of its own), 1 (hip/myers_rerank.hip) or
+    2 (hip/myers_rerank_strips.hip), the strips it is walked in and their width in 32-bit words, and the bytes of parked deltas
+    the strips launch would allocate.  The `rerank` knob applies as it does to the call."""
+    import numpy as np
+
+    lengths = np.ascontiguousarray(query_lengths, dtype=np.uint32)
+    routes, strips = np.zeros(len(lengths), np.uint8), np.zeros(len(lengths), np.uint32)
+    strip_words, scratch = np.zeros(len(lengths), np.uint32), c_size_t(0)
+    status = lib.szs_rocm_rerank_probe(int(unit_cost), int(runes), lengths.ctypes.data, len(lengths), k, longest_candidate, routes.ctypes.data,
+                                       strips.ctypes.data, strip_words.ctypes.data, ctypes.addressof(scratch))
+    if status != 0:
+        raise StringZillasError(status, None)
+    return routes, strips, strip_words, int(scratch.value)
 
 
 def team_shapes():

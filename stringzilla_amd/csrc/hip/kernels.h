@@ -296,6 +296,29 @@ int szs_hip_levenshtein_rerank(szs_rerank_side_t const *queries, szs_rerank_side
                                uint64_t *scores, uint64_t scores_stride, unsigned widest, uint32_t *flags, unsigned long long *counters,
                                void *stream);
 
+/**
+ *  Rerank rows whose query is longer than that (hip/myers_rerank_strips.hip): the same rows, groups, indices, flags and counters,
+ *  the query walked as STRIPS of 1 ... 8 words - as few as 8 words allow, all of one width (a 300-byte query: two strips of 5
+ *  words) - with the horizontal deltas under a strip's last row parked in `parked`, 16 text columns to a dword.  `rows` should
+ *  arrive by DESCENDING word count of the query: the rows of a wavefront run at the strip count and width of its longest query.
+ *  Every query of `rows` has at most SZS_RERANK_LONGEST_STRIPS_QUERY bytes (shorter ones, 256 bytes and less included, are scored
+ *  correctly); a longer one sets `flags[SZS_RERANK_FLAG_UNFIT]`.  The grid is persistent: `workgroups` one-wavefront workgroups
+ *  stride over the rows, and `parked` holds workgroups x 64 x parked_dwords dwords of device memory (no need to clear it).  A
+ *  listed candidate of more than 16 x parked_dwords bytes is not scored and sets `flags[SZS_RERANK_FLAG_UNFIT]`.
+ *
+ *  64 KiB is a design bound, not a measured one: beyond it one lane's serial chain of len(q) / 256 x len(c) columns is the wrong
+ *  tool, and the engine's chained few-pairs tiers (hip/myers_chain.hip), which the row route reaches, are built for such pairs.
+ */
+#define SZS_RERANK_LONGEST_STRIPS_QUERY 65536u
+#define SZS_RERANK_STRIP_WORDS 8u /* the widest strip: 256 rows */
+#define SZS_RERANK_WORDS_OF(length) ((length) ? ((length) + 31u) / 32u : 1u)
+#define SZS_RERANK_STRIPS_OF(words) (((words) + SZS_RERANK_STRIP_WORDS - 1u) / SZS_RERANK_STRIP_WORDS)
+#define SZS_RERANK_STRIP_WORDS_OF(words) (((words) + SZS_RERANK_STRIPS_OF(words) - 1u) / SZS_RERANK_STRIPS_OF(words))
+int szs_hip_levenshtein_rerank_strips(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,
+                                      uint32_t const *rows, uint32_t rows_count, uint64_t const *indices, uint64_t indices_stride,
+                                      uint64_t k, uint64_t *scores, uint64_t scores_stride, uint32_t workgroups, uint32_t *parked,
+                                      uint32_t parked_dwords, uint32_t *flags, unsigned long long *counters, void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {
@@ -329,8 +352,9 @@ enum {
     szs_knob_tiny_k,        /* -1 automatic (tiny tokens on both sides) | 0 never | 1 every unit-cost byte call of strings up to 255 bytes, few
                                of them beyond 16: the tiny-token launch of hip/myers_tiny.hip | 2 (testing): dense batches are scored there too */
     szs_knob_top_k_tile_k,  /* -1 automatic | n: the most candidates per scored tile of a top-k call (host/top_k.c) */
-    szs_knob_rerank_k,      /* -1 automatic (rows of a unit-cost byte engine whose query has at most 256 bytes: hip/myers_rerank.hip) |
-                               0: every row of a rerank call as an engine call of its own (host/rerank.c) */
+    szs_knob_rerank_k,      /* -1 automatic (rows of a unit-cost byte engine: a query of at most 256 bytes by hip/myers_rerank.hip, one of
+                               at most 64 KiB by hip/myers_rerank_strips.hip) | 0: every row of a rerank call as an engine call of its
+                               own (host/rerank.c) | 1: the short kernel only, longer rows as engine calls (the A/B leg of the strips) */
     szs_knob_count_k
 };
 int szs_tuning_get(int knob);

@@ -19,44 +19,11 @@
  *    kind of failure has a flag word of its own and every lane stores the same 1 there: what the host reads does not depend on
  *    which lane stored last.
  *  - Scores leave as ordinary 8-byte vector stores, straight into the caller's rows.
+ *  (rerank_fetch, rerank_bits_in_word and wave_sum_u64 are hip/rerank_core.hpp's, shared with hip/myers_rerank_strips.hip.)
  */
-#include "myers_core.hpp"
+#include "rerank_core.hpp"
 
 namespace szs_hip {
-
-/** The bits of [from, to) that fall into word `w` (`from` differs per row of the wavefront: the rows' own phantom rows). */
-__device__ __forceinline__ u32 rerank_bits_in_word(u32 from, u32 to, int w) {
-    u32 const low = from > 32u * w ? from : 32u * w, high = to < 32u * w + 32u ? to : 32u * w + 32u;
-    if (low >= high) return 0u;
-    return (high - low == 32u ? ~0u : (1u << (high - low)) - 1u) << (low - 32u * w);
-}
-
-/** String `index` of a side, `index < side.count` checked by the caller.  False: its offsets descend, or it has 4 GiB or more. */
-__device__ __forceinline__ bool rerank_fetch(szs_rerank_side_t const &side, u64 index, u64 &address, u32 &length) {
-    if (side.refs) {
-        szs_string_ref_t const ref = side.refs[index];
-        address = ref.address, length = ref.length;
-        return true;
-    }
-    u64 from, to;
-    if (side.wide) {
-        u64 const *offsets = static_cast<u64 const *>(side.offsets);
-        from = offsets[index], to = offsets[index + 1];
-    }
-    else {
-        u32 const *offsets = static_cast<u32 const *>(side.offsets);
-        from = offsets[index], to = offsets[index + 1];
-    }
-    if (to < from || to - from > 0xFFFFFFFFull) return false;
-    address = side.base + from, length = (u32)(to - from);
-    return true;
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 value) {
-#pragma unroll
-    for (int offset = 32; offset >= 1; offset >>= 1) value += (u64)__shfl_xor((unsigned long long)value, offset, 64);
-    return value;
-}
 
 /**
  *  The rows of one wavefront at `words_` words: every group of `lanes_` lanes builds its row's table, then scores the row's listed

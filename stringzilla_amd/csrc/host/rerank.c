@@ -2,18 +2,25 @@
  *  rerank.c - exact scores of LISTED candidates per query (szs_rocm_rerank*, include/stringzillas/stringzillas_rocm.h; DESIGN.md
  *  section 4.8): scores[q][r] = score(queries[q], candidates[indices[q][r]]), the cell the matrix call would put there.
  *
- *  Two routes inside one call, chosen per row:
+ *  Three routes inside one call, chosen per row (rerank_route_of):
  *    - the KERNEL route (hip/myers_rerank.hip): rows of a unit-cost byte Levenshtein engine whose query has at most 256 bytes.  All
  *      such rows of a block go into one launch, dealt by descending query length; the kernel reads the indices and writes the scores
  *      where they are when the device can reach them, else through a dense copy of the block;
- *    - the ROW route: every other row - and every row with the `rerank` knob at 0 - is one ordinary engine call
- *      (szs_engine_cross) of 1 x k' over a gathered sequence of the row's non-empty indices, scattered into the row on the host.
+ *    - the STRIPS route (hip/myers_rerank_strips.hip): rows of such an engine whose query has more than 256 and at most 65,536 bytes
+ *      (SZS_RERANK_LONGEST_STRIPS_QUERY), candidates of any length that the parked scratch can hold (rerank_strips_grid).  All such
+ *      rows of a block go into one launch of their own, dealt by descending word count of the query.  64 KiB is a design bound, not
+ *      a measured one: above it one lane's serial chain of len(q) / 256 x len(c) columns is the wrong tool, and the engine's chained
+ *      few-pairs tiers, which the row route reaches, are built for such pairs;
+ *    - the ROW route: every other row - and every row with the `rerank` knob at 0, every long row with it at 1 - is one ordinary
+ *      engine call (szs_engine_cross) of 1 x k' over a gathered sequence of the row's non-empty indices, scattered into the row on
+ *      the host.
  *  Indices the host can read are validated before anything is launched; indices only the device can read are checked by the kernel
  *  (`index < count` before every use, a flag in pinned memory) - or, for the rows of the row route, downloaded and validated first.
  *
  *  szs_engine_rerank checks the arguments, lays out the scratch (rerank_layout), prepares the sides and walks the blocks; per block:
- *  rerank_deal_rows (which rows the kernel takes, longest query first), rerank_kernel_rows (staging, the launch, the scores home),
- *  rerank_row (the row route).  The two routes write disjoint rows of `scores`, so neither depends on running before the other.
+ *  rerank_deal_rows and rerank_deal_strip_rows (which rows each kernel takes, longest query first), rerank_kernel_rows (staging, at
+ *  most one launch of each kernel, the scores home), rerank_row (the row route).  The routes write disjoint rows of `scores`, so none
+ *  depends on running before another.  szs_rocm_rerank_probe reports the routing of bare lengths through the same functions.
  */
 #include "szs_internal.h"
 
@@ -23,6 +30,11 @@
 #define SZS_RERANK_STAGE_BYTES ((size_t)128 << 20) /* a block's dense copy of indices or scores the device cannot reach */
 #define SZS_RERANK_MOST_ROWS ((size_t)1 << 20)     /* rows of a block: bounds the kernel's row list */
 #define SZS_RERANK_EMPTY (~(uint64_t)0)            /* SZ_SIZE_MAX: the empty slot top-k emits */
+#define SZS_RERANK_PARKED_BYTES ((size_t)256 << 20) /* the parked deltas of the strips launch: a chosen budget (what top-k and the
+                                                       fingerprint search give their staging), not a measurement */
+#define SZS_RERANK_STRIPS_TABLES 5120u             /* 8 KB tables that 256 CUs x 160 KB of LDS hold: the most rows in flight */
+
+enum { szs_rerank_route_row_k = 0, szs_rerank_route_kernel_k = 1, szs_rerank_route_strips_k = 2 };
 
 static double now_milliseconds(void) {
     struct timespec ts;
@@ -194,9 +206,11 @@ typedef struct {
     uint64_t const *indices;
     uint64_t *scores;
     int scores_on_host, stage_indices, stage_scores;
-    int kernel_route;
+    int device;
+    int kernel_route, strips_route; /* may rows take hip/myers_rerank.hip, and hip/myers_rerank_strips.hip */
+    uint64_t longest_candidate;     /* strips_route: over the whole candidate side */
     szs_rerank_side_t sides[2];
-    uint32_t *query_lengths; /* kernel_route: per query, ~0 where the kernel does not take it */
+    uint32_t *query_lengths; /* kernel_route: per query, ~0 where no kernel takes it */
     uint64_t *picks, *landed, *row_cells, *row_image;
     uint32_t *flags, *order, *device_order;
     unsigned long long *device_counters;
@@ -204,44 +218,114 @@ typedef struct {
     int engine_calls;
 } szs_rerank_call_t;
 
-static int row_takes_kernel(szs_rerank_call_t const *call, size_t query) {
-    return call->kernel_route && call->query_lengths[query] <= SZS_RERANK_LONGEST_QUERY;
+/** Which kernels the rows of a call may take: by the engine (unit-cost byte Levenshtein) and the `rerank` knob. */
+static void rerank_routes_enabled(int unit_cost_bytes, int *kernel_route, int *strips_route) {
+    int const knob = szs_tuning_get(szs_knob_rerank_k);
+    *kernel_route = knob != 0 && unit_cost_bytes;
+    *strips_route = *kernel_route && knob != 1;
 }
 
-/** The kernel's rows of block [q0, q0 + rows) into `order`, longest query first (a counting sort of the lengths 256 ... 0). */
-static size_t rerank_deal_rows(szs_rerank_call_t const *call, size_t q0, size_t rows, uint32_t *longest) {
+/** The route of a row whose query has `length` bytes (~0: more than any kernel takes, or unknown). */
+static int rerank_route_of(int kernel_route, int strips_route, uint32_t length) {
+    if (kernel_route && length <= SZS_RERANK_LONGEST_QUERY) return szs_rerank_route_kernel_k;
+    if (strips_route && length != ~0u && length <= SZS_RERANK_LONGEST_STRIPS_QUERY) return szs_rerank_route_strips_k;
+    return szs_rerank_route_row_k;
+}
+
+/**
+ *  The persistent grid of the strips launch over `rows` rows of `k` slots and its parked scratch: one dword per 16 columns of the
+ *  longest candidate for each of a workgroup's 64 lanes.  At most as many workgroups as rows need, as tables fit the device's LDS,
+ *  and as keep the scratch within SZS_RERANK_PARKED_BYTES - fewer when one very long candidate asks for it; `workgroups` 0: even one
+ *  workgroup's scratch is beyond the budget (a candidate of more than 16 MiB), the strips route is not taken.
+ */
+typedef struct {
+    uint32_t workgroups, parked_dwords;
+    size_t bytes;
+} szs_rerank_strips_grid_t;
+
+static szs_rerank_strips_grid_t rerank_strips_grid(size_t rows, size_t k, uint64_t longest_candidate) {
+    szs_rerank_strips_grid_t grid = {0, 0, 0};
+    uint64_t const dwords = longest_candidate ? (longest_candidate + 15) / 16 : 1;
+    uint64_t const workgroup_bytes = dwords * 64 * sizeof(uint32_t);
+    if (workgroup_bytes > SZS_RERANK_PARKED_BYTES) return grid;
+    size_t const groups = 64 / szs_hip_rerank_lanes(k);
+    size_t workgroups = (rows + groups - 1) / groups;
+    if (workgroups > SZS_RERANK_STRIPS_TABLES / groups) workgroups = SZS_RERANK_STRIPS_TABLES / groups;
+    if (workgroups > SZS_RERANK_PARKED_BYTES / workgroup_bytes) workgroups = SZS_RERANK_PARKED_BYTES / workgroup_bytes;
+    if (workgroups < 1) workgroups = 1;
+    grid.workgroups = (uint32_t)workgroups, grid.parked_dwords = (uint32_t)dwords, grid.bytes = workgroups * (size_t)workgroup_bytes;
+    return grid;
+}
+
+static int row_route(szs_rerank_call_t const *call, size_t query) {
+    return call->kernel_route ? rerank_route_of(call->kernel_route, call->strips_route, call->query_lengths[query]) : szs_rerank_route_row_k;
+}
+
+/** The short kernel's rows of block [q0, q0 + rows) into `order`, longest query first (a counting sort of the lengths 256 ... 0). */
+static size_t rerank_deal_rows(szs_rerank_call_t const *call, size_t q0, size_t rows, uint32_t *order, uint32_t *longest) {
     *longest = 0;
     if (!call->kernel_route) return 0;
     uint32_t bins[SZS_RERANK_LONGEST_QUERY + 2];
     size_t kernel_rows = 0;
     memset(bins, 0, sizeof(bins));
     for (size_t r = 0; r < rows; ++r)
-        if (row_takes_kernel(call, q0 + r)) ++bins[SZS_RERANK_LONGEST_QUERY - call->query_lengths[q0 + r] + 1], ++kernel_rows;
+        if (row_route(call, q0 + r) == szs_rerank_route_kernel_k) ++bins[SZS_RERANK_LONGEST_QUERY - call->query_lengths[q0 + r] + 1], ++kernel_rows;
     for (size_t b = 1; b < SZS_RERANK_LONGEST_QUERY + 2; ++b) bins[b] += bins[b - 1];
     for (size_t r = 0; r < rows; ++r) {
-        if (!row_takes_kernel(call, q0 + r)) continue;
+        if (row_route(call, q0 + r) != szs_rerank_route_kernel_k) continue;
         uint32_t const length = call->query_lengths[q0 + r];
-        call->order[bins[SZS_RERANK_LONGEST_QUERY - length]++] = (uint32_t)r;
+        order[bins[SZS_RERANK_LONGEST_QUERY - length]++] = (uint32_t)r;
         if (length > *longest) *longest = length;
     }
     return kernel_rows;
 }
 
 /**
- *  The kernel route of one block: stages what the device cannot reach, launches once, brings the scores home, reads the flags.
- *  Staged scores go home by RUNS of consecutive kernel rows - one 2-D copy when the kernel took the whole block - so the rows of
- *  the row route are never written from here.
+ *  The strips kernel's rows of the block into `order`, most words first (a counting sort of the word counts 2048 ... 9): the rows of
+ *  a wavefront then share a strip count, and mostly a strip width.
  */
-static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t rows, size_t kernel_rows, uint32_t longest,
-                                      hipError_t *hip_error, char const **error_message) {
+static size_t rerank_deal_strip_rows(szs_rerank_call_t const *call, size_t q0, size_t rows, uint32_t *order, uint32_t *longest) {
+    enum { most_words = SZS_RERANK_LONGEST_STRIPS_QUERY / 32 };
+    *longest = 0;
+    if (!call->strips_route) return 0;
+    uint32_t bins[most_words + 2];
+    size_t strip_rows = 0;
+    memset(bins, 0, sizeof(bins));
+    for (size_t r = 0; r < rows; ++r)
+        if (row_route(call, q0 + r) == szs_rerank_route_strips_k)
+            ++bins[most_words - SZS_RERANK_WORDS_OF(call->query_lengths[q0 + r]) + 1], ++strip_rows;
+    for (size_t b = 1; b < most_words + 2; ++b) bins[b] += bins[b - 1];
+    for (size_t r = 0; r < rows; ++r) {
+        if (row_route(call, q0 + r) != szs_rerank_route_strips_k) continue;
+        uint32_t const length = call->query_lengths[q0 + r];
+        order[bins[most_words - SZS_RERANK_WORDS_OF(length)]++] = (uint32_t)r;
+        if (length > *longest) *longest = length;
+    }
+    return strip_rows;
+}
+
+/**
+ *  The two kernel routes of one block: stages what the device cannot reach, launches each kernel at most once - the short rows are
+ *  order[0 .. short_rows), the strips rows follow them - brings the scores home, reads the flags.  Staged scores go home by RUNS of
+ *  consecutive rows of either kernel - one 2-D copy when the kernels took the whole block - so the rows of the row route are never
+ *  written from here.
+ */
+static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t rows, size_t short_rows, uint32_t longest_short,
+                                      size_t strip_rows, uint32_t longest_strips, hipError_t *hip_error, char const **error_message) {
     szs_engine_s *const engine = call->engine;
     hipStream_t const stream = call->stream;
     size_t const k = call->k, row_stride = call->row_stride, row_bytes = k * sizeof(uint64_t);
+    szs_rerank_strips_grid_t const grid = rerank_strips_grid(strip_rows, k, call->longest_candidate);
+    if (strip_rows) {
+        sz_status_t const status = szs_buffer_reserve(&engine->device_rerank_parked, szs_memory_device_k, call->device, grid.bytes, error_message);
+        if (status != sz_success_k) return status;
+    }
     uint64_t *const staged = (uint64_t *)engine->device_rerank_staged.pointer;
     uint64_t const *kernel_indices = call->indices + q0 * row_stride;
     uint64_t *kernel_scores = call->scores + q0 * row_stride;
     size_t kernel_indices_stride = row_stride, kernel_scores_stride = row_stride;
-    unsigned const widest = longest ? (longest + 31) / 32 : 1;
+    unsigned const widest = longest_short ? (longest_short + 31) / 32 : 1;
+    uint32_t const longest = longest_short > longest_strips ? longest_short : longest_strips;
     hipError_t error = hipSuccess;
     if (call->stage_indices) {
         error = hipMemcpy2DAsync(staged, row_bytes, call->indices + q0 * row_stride, row_stride * sizeof(uint64_t), row_bytes, rows,
@@ -252,21 +336,27 @@ static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t
     memset(call->flags, 0, SZS_RERANK_FLAGS * sizeof(uint32_t));
     if (error == hipSuccess) error = hipMemsetAsync(call->device_counters, 0, 3 * sizeof(uint64_t), stream);
     if (error == hipSuccess)
-        error = hipMemcpyAsync(call->device_order, call->order, kernel_rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        error = hipMemcpyAsync(call->device_order, call->order, (short_rows + strip_rows) * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
     if (error == hipSuccess) error = hipEventRecord(engine->event_start, stream);
-    if (error == hipSuccess)
-        error = (hipError_t)szs_hip_levenshtein_rerank(&call->sides[0], &call->sides[1], q0, call->device_order, (uint32_t)kernel_rows,
+    if (error == hipSuccess && short_rows)
+        error = (hipError_t)szs_hip_levenshtein_rerank(&call->sides[0], &call->sides[1], q0, call->device_order, (uint32_t)short_rows,
                                                        kernel_indices, kernel_indices_stride, k, kernel_scores, kernel_scores_stride, widest,
                                                        call->flags, call->device_counters, stream);
+    if (error == hipSuccess && strip_rows)
+        error = (hipError_t)szs_hip_levenshtein_rerank_strips(&call->sides[0], &call->sides[1], q0, call->device_order + short_rows,
+                                                              (uint32_t)strip_rows, kernel_indices, kernel_indices_stride, k, kernel_scores,
+                                                              kernel_scores_stride, grid.workgroups,
+                                                              (uint32_t *)engine->device_rerank_parked.pointer, grid.parked_dwords,
+                                                              call->flags, call->device_counters, stream);
     if (error == hipSuccess) error = hipEventRecord(engine->event_stop, stream);
     if (error == hipSuccess) error = hipMemcpyAsync(call->landed, call->device_counters, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
     for (size_t r = 0; r < rows && error == hipSuccess && call->stage_scores;) {
-        if (!row_takes_kernel(call, q0 + r)) {
+        if (row_route(call, q0 + r) == szs_rerank_route_row_k) {
             ++r;
             continue;
         }
         size_t run = r + 1;
-        while (run < rows && row_takes_kernel(call, q0 + run)) ++run;
+        while (run < rows && row_route(call, q0 + run) != szs_rerank_route_row_k) ++run;
         error = hipMemcpy2DAsync(call->scores + (q0 + r) * row_stride, row_stride * sizeof(uint64_t), kernel_scores + r * k, row_bytes, row_bytes,
                                  run - r, hipMemcpyDeviceToHost, stream);
         r = run;
@@ -277,13 +367,14 @@ static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t
         *hip_error = error;
         return sz_success_k;
     }
-    if (call->flags[SZS_RERANK_FLAG_UNFIT]) return szs_report(sz_status_unknown_k, error_message, "A query beyond the rerank kernel's width");
+    if (call->flags[SZS_RERANK_FLAG_UNFIT]) return szs_report(sz_status_unknown_k, error_message, "A query or a candidate beyond what the rerank kernels were sized for");
     if (call->flags[SZS_RERANK_FLAG_TAPE]) return szs_report(sz_unexpected_dimensions_k, error_message, "Tape offsets must ascend");
     if (call->flags[SZS_RERANK_FLAG_INDEX]) return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
     float milliseconds = 0;
     if (hipEventElapsedTime(&milliseconds, engine->event_start, engine->event_stop) != hipSuccess) (void)hipGetLastError();
     szs_rocm_call_profile_t *const total = &call->total;
-    total->kernel_milliseconds += milliseconds, total->launches += 1, total->pairs += call->landed[0], total->cells += call->landed[1];
+    total->kernel_milliseconds += milliseconds, total->launches += (short_rows != 0) + (strip_rows != 0);
+    total->pairs += call->landed[0], total->cells += call->landed[1];
     total->algorithmic_bytes += call->landed[2] + call->landed[0] * (2 * 4 + 8);
     if (longest > total->longest_query) total->longest_query = longest;
     return sz_success_k;
@@ -370,7 +461,8 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     if (block < 1) block = 1;
     call.block = block;
 
-    call.kernel_route = szs_tuning_get(szs_knob_rerank_k) != 0 && engine->family == szs_family_levenshtein_k && engine->is_unit_cost;
+    call.device = device;
+    rerank_routes_enabled(engine->family == szs_family_levenshtein_k && engine->is_unit_cost, &call.kernel_route, &call.strips_route);
     int const refs_needed[2] = {call.kernel_route && side_needs_refs(queries), call.kernel_route && candidates && side_needs_refs(candidates)};
     size_t const refs_count[2] = {refs_needed[0] ? q_count : 0, refs_needed[1] ? c_count : 0};
     size_t const gathered = refs_count[0] > refs_count[1] ? refs_count[0] : refs_count[1];
@@ -409,7 +501,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
             if (refs_needed[0]) call.query_lengths[q] = lengths[q];
             else {
                 uint64_t const from = tape_offset(queries, call.query_offsets, q), to = tape_offset(queries, call.query_offsets, q + 1);
-                call.query_lengths[q] = to >= from && to - from <= SZS_RERANK_LONGEST_QUERY ? (uint32_t)(to - from) : ~0u;
+                call.query_lengths[q] = to >= from && to - from <= SZS_RERANK_LONGEST_STRIPS_QUERY ? (uint32_t)(to - from) : ~0u;
             }
         }
         if (call.kernel_route && candidates) {
@@ -420,13 +512,33 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
         }
         else if (call.kernel_route)
             call.sides[1] = call.sides[0];
+        /* the strips route: sized by the longest string of the candidate side - looked for only when a row would take it */
+        int wanted = 0;
+        for (size_t q = 0; q < q_count && call.kernel_route && call.strips_route && !wanted; ++q)
+            wanted = row_route(&call, q) == szs_rerank_route_strips_k;
+        if (!call.kernel_route || !wanted) call.strips_route = 0;
+        else {
+            int const pool_side = candidates ? 1 : 0;
+            for (size_t i = 0; i < c_count; ++i) {
+                uint64_t length = 0;
+                if (refs_needed[pool_side]) length = lengths[i]; /* the side gathered last: the candidates', or the queries' own */
+                else {
+                    uint64_t const from = tape_offset(call.pool, call.pool_offsets, i), to = tape_offset(call.pool, call.pool_offsets, i + 1);
+                    length = to >= from ? to - from : 0; /* (descending offsets: the kernel reports them) */
+                }
+                if (length > call.longest_candidate) call.longest_candidate = length;
+            }
+            if (!rerank_strips_grid(1, k, call.longest_candidate).workgroups) call.strips_route = 0; /* those rows: the row route */
+        }
     }
 
     hipError_t error = hipSuccess;
     for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block) {
         size_t const rows = q_count - q0 < block ? q_count - q0 : block;
-        uint32_t longest = 0;
-        size_t const kernel_rows = rerank_deal_rows(&call, q0, rows, &longest);
+        uint32_t longest_short = 0, longest_strips = 0;
+        size_t const short_rows = rerank_deal_rows(&call, q0, rows, call.order, &longest_short);
+        size_t const strip_rows = rerank_deal_strip_rows(&call, q0, rows, call.order + short_rows, &longest_strips);
+        size_t const kernel_rows = short_rows + strip_rows;
 
         /* the rows of the row route need their indices on the host: downloaded and validated before anything is launched */
         uint64_t const *host_indices = call.indices + q0 * row_stride;
@@ -443,9 +555,10 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
             host_indices = downloaded, host_indices_stride = k;
         }
 
-        if (kernel_rows) status = rerank_kernel_rows(&call, q0, rows, kernel_rows, longest, &error, error_message);
+        if (kernel_rows)
+            status = rerank_kernel_rows(&call, q0, rows, short_rows, longest_short, strip_rows, longest_strips, &error, error_message);
         for (size_t r = 0; r < rows && kernel_rows < rows && status == sz_success_k && error == hipSuccess; ++r)
-            if (!row_takes_kernel(&call, q0 + r)) status = rerank_row(&call, q0 + r, host_indices + r * host_indices_stride, &error, error_message);
+            if (row_route(&call, q0 + r) == szs_rerank_route_row_k) status = rerank_row(&call, q0 + r, host_indices + r * host_indices_stride, &error, error_message);
     }
     hipError_t const drained = hipStreamSynchronize(stream); /* synchronous, also when it fails */
     if (status != sz_success_k) return status;
@@ -460,4 +573,27 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     engine->last_profile.longest_query = total->longest_query, engine->last_profile.longest_candidate = total->longest_candidate;
     engine->last_profile.host_milliseconds = now_milliseconds() - started;
     return szs_report(sz_success_k, error_message, NULL);
+}
+
+/* ---- the exported probe ----------------------------------------------------------------------------------------------------- */
+
+sz_status_t szs_rocm_rerank_probe(int unit_cost, int runes, sz_u32_t const *query_lengths, sz_size_t queries_count, sz_size_t k,
+                                  sz_size_t longest_candidate, sz_u8_t *routes, sz_u32_t *strips, sz_u32_t *strip_words,
+                                  sz_size_t *scratch_bytes) {
+    if (k < 1 || (queries_count && !query_lengths)) return sz_unexpected_dimensions_k;
+    int kernel_route = 0, strips_route = 0;
+    rerank_routes_enabled(unit_cost && !runes, &kernel_route, &strips_route);
+    if (!rerank_strips_grid(1, k, longest_candidate).workgroups) strips_route = 0;
+    size_t strip_rows = 0;
+    for (size_t q = 0; q < queries_count; ++q) {
+        int const route = rerank_route_of(kernel_route, strips_route, query_lengths[q]);
+        uint32_t const words = SZS_RERANK_WORDS_OF(query_lengths[q]);
+        strip_rows += route == szs_rerank_route_strips_k;
+        if (routes) routes[q] = (sz_u8_t)route;
+        /* the short kernel: one bit-vector of the query's own words - what the strips rule gives up to 8 words; the row route: none */
+        if (strips) strips[q] = route == szs_rerank_route_row_k ? 0 : SZS_RERANK_STRIPS_OF(words);
+        if (strip_words) strip_words[q] = route == szs_rerank_route_row_k ? 0 : SZS_RERANK_STRIP_WORDS_OF(words);
+    }
+    if (scratch_bytes) *scratch_bytes = strip_rows ? rerank_strips_grid(strip_rows, k, longest_candidate).bytes : 0;
+    return sz_success_k;
 }

@@ -161,6 +161,7 @@ typedef struct szs_engine_s {
     szs_buffer_t pinned_rerank;          /* pinned: the kernel's flag, its counters, a row's cells and image, the kernel's rows, refs of both sides */
     szs_buffer_t device_rerank;          /* device: the counters, the kernel's rows, the refs */
     szs_buffer_t device_rerank_staged;   /* device: dense indices, then scores, of a block whose arrays the device cannot reach */
+    szs_buffer_t device_rerank_parked;   /* device: the parked deltas of the strips kernel, workgroups x 64 x ceil(longest candidate / 16) dwords */
 
     szs_rocm_call_profile_t last_profile;
 } szs_engine_s;
