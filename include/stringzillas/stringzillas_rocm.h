@@ -5,6 +5,8 @@
  *  - szs_rocm_last_call_profile : device-event kernel time and work counters of the last engine call - the
  *    counterpart of the reference's `cuda_status_t::elapsed_milliseconds` / "Kernel GCUPS"
  *    (/root/reference/include/stringzillas/types.cuh:280-298,482-534; bench/similarities.cuh:303-308).
+ *  - szs_rocm_last_pairing, szs_rocm_pair_rule_probe : which two queries shared a workgroup of the short launch that plans itself
+ *    (csrc/hip/pair_rule.h) - what the last call's sorter chose, and the same choice on bare lengths without a GPU.
  *  - szs_rocm_shard_rows        : longest-processing-time assignment of query rows to N GPUs;
  *    the reference has no multi-GPU path at all (one engine call = one device, stringzillas.h:137).
  *  - szs_rocm_rerank_probe, szs_rocm_plan_probe, szs_rocm_orientation_probe, szs_rocm_team_orientation_probe, szs_rocm_launch_order_probe,
@@ -55,6 +57,24 @@ typedef struct szs_rocm_call_profile_t {
 
 /** Copies the profile of the most recent call made through `engine` (any of the four engine handle types). */
 SZ_API_RUNTIME sz_status_t szs_rocm_last_call_profile(void *engine, szs_rocm_call_profile_t *profile);
+
+/**
+ *  The pairing rule of the most recent call made through `engine`: which two queries shared a workgroup of the short launch that
+ *  plans itself (planner mode 4).  Queries ranked by descending length, slots = ceil(Q / 2), n = Q - slots: 0 - slot s < n scored
+ *  ranks s and slots + s; delta + 1 - ranks s and slots + ((n - 1 - s + delta) mod n).  0 also when the call took another way.
+ */
+SZ_API_RUNTIME sz_u32_t szs_rocm_last_pairing(void *engine);
+
+/**
+ *  The same choice on bare lengths (any order), without a GPU.  `*rule` in: SZS_ROCM_PAIR_RULE_CHOOSE - choose as the launch
+ *  does (rule 0 and sixteen evenly spaced shifts delta = k n / 16; the fewest words win, ties to rule 0, then to the smallest
+ *  shift; more than 1024 queries, or one beyond 256 bytes: rule 0) - or a rule <= n to evaluate.  `*rule` out: the rule;
+ *  `total_words` (optional): the bit-vector words per text column, summed over the slots; `slot_pairs_out` (optional, 2 x slots
+ *  entries): the descending ranks of every slot's two queries, 0xFFFFFFFF where a slot has no second one.
+ */
+#define SZS_ROCM_PAIR_RULE_CHOOSE 0xFFFFFFFFu
+SZ_API_RUNTIME sz_status_t szs_rocm_pair_rule_probe(sz_u32_t const *lengths, sz_size_t count, sz_u32_t *rule, sz_u64_t *total_words,
+                                                    sz_u32_t *slot_pairs_out);
 
 /**
  *  Deals `rows` query rows to `shards` devices so that the summed `row_weights` per shard are as equal as the

@@ -113,6 +113,8 @@ SIGNATURES = {
     "szs_fingerprints_free": (None, [c_void_p]),
     # ROCm-only additions (include/stringzillas/stringzillas_rocm.h)
     "szs_rocm_last_call_profile": (c_int, [c_void_p, ctypes.POINTER(CallProfile)]),
+    "szs_rocm_last_pairing": (ctypes.c_uint32, [c_void_p]),
+    "szs_rocm_pair_rule_probe": (c_int, [c_void_p, c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), c_void_p]),
     "szs_rocm_shard_rows": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     "szs_rocm_shard_triangle": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     "szs_rocm_plan_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -209,6 +211,24 @@ def rerank_probe(query_lengths, k, longest_candidate, unit_cost=True, runes=Fals
     if status != 0:
         raise StringZillasError(status, None)
     return routes, strips, strip_words, int(scratch.value)
+
+
+PAIR_RULE_CHOOSE = 0xFFFFFFFF
+
+
+def pair_rule_probe(lengths, rule=PAIR_RULE_CHOOSE):
+    """`szs_rocm_pair_rule_probe`: which two queries of these byte lengths share a workgroup of the short launch that plans itself -
+    no GPU involved.  `rule`: PAIR_RULE_CHOOSE for the sorter's own choice, or a rule to evaluate.  Returns (rule, total_words,
+    slot_pairs): slot_pairs[s] holds the descending ranks of slot s's two queries, -1 where it has no second one."""
+    import numpy as np
+
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    slot_pairs = np.zeros(((len(lengths) + 1) // 2, 2), np.uint32)
+    chosen, total = ctypes.c_uint32(rule), ctypes.c_uint64(0)
+    status = lib.szs_rocm_pair_rule_probe(lengths.ctypes.data, len(lengths), ctypes.byref(chosen), ctypes.byref(total), slot_pairs.ctypes.data)
+    if status != 0:
+        raise StringZillasError(status, None)
+    return int(chosen.value), int(total.value), slot_pairs.astype(np.int64) - (slot_pairs == 0xFFFFFFFF) * (1 << 32)
 
 
 def team_shapes():

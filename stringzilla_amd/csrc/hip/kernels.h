@@ -436,7 +436,8 @@ int szs_hip_plan(szs_plan_side_t const *queries, szs_plan_side_t const *candidat
  *  short kernel (<= 256 bytes) and whose sides hold at most SZS_FUSED_MOST_STRINGS strings is ONE launch and nothing else.
  *  Workgroup 0 sorts the kernel's query side, workgroup 1 its candidate side (a counting sort of the lengths in LDS, 256
  *  threads, ~2 us), each writes the side's ascending and descending refs - exactly what szs_hip_plan writes - and publishes
- *  `ready[side] = sequence` (release, agent scope); every workgroup waits for both words (acquire) before it reads a ref.
+ *  `ready[side] = sequence` (release, agent scope); every workgroup waits for both words before it reads a ref.  The query side's
+ *  sorter also chooses which two queries share a workgroup (hip/pair_rule.h) and publishes the rule in the same 64-bit word.
  *  Workgroups are dispatched in order, so the two sorters are resident before anyone can wait for them.  No planner launch,
  *  no kernel boundary between planning and scoring (config 2: 12 + 5 of a 202 us call).
  *  A side whose offsets are malformed, or a query side with a string beyond 256 bytes, is written BLANK (every length 0:
@@ -451,7 +452,7 @@ typedef struct szs_fused_side_report_t {
     uint32_t sequence; /* of the launch that wrote this report */
     uint32_t status;   /* SZS_PLAN_STATUS_DESCENDING | SZS_PLAN_STATUS_OVERFLOW */
     uint32_t blank;    /* the side's refs were written with length 0: nothing real was scored */
-    uint32_t reserved;
+    uint32_t pairing;  /* the query side's: the rule its sorter published (hip/pair_rule.h); 0 on the candidate side */
     szs_side_stats_t stats;
     uint32_t rank_lengths[SZS_PLAN_RANK_SAMPLES + 1];
     uint32_t ticks[5]; /* 100 MHz: the sorter's begin; offsets loaded; positions known; refs written; published - all relative to [0] but [0] itself */
@@ -461,7 +462,8 @@ typedef struct szs_fused_side_report_t {
 typedef struct szs_fused_plan_t {
     szs_plan_side_t side[2]; /* KERNEL roles: [0] its queries (patterns; scored from .descending), [1] its candidates (.ascending) */
     uint32_t sequence;       /* never 0 */
-    uint32_t *ready;         /* device memory: ready[0] and ready[32], zeroed when allocated; a launch leaves `sequence` in both */
+    uint32_t *ready;         /* device memory: ready[0] and ready[32], zeroed when allocated; a launch leaves `sequence` in both - and
+                                the query side's pairing rule in ready[1]: the two are ONE 64-bit word, written and read at once */
     szs_fused_side_report_t *report; /* [2], pinned host memory */
     uint32_t *gave_up;       /* pinned host memory: a waiting workgroup whose polls ran out leaves `sequence` here and scores nothing -
                                 the host then plans the call the ordinary way (a launch never hangs on a sorter that does not publish) */

@@ -38,9 +38,19 @@
  */
 #include "myers_core.hpp"
 
+#define SZS_PAIR_RULE_FN __host__ __device__ static inline
+#include "pair_rule.h"
+
 #include <cstdlib>
 
 namespace szs_hip {
+
+#ifndef SZS_MYERS_PACK_QUERIES
+#define SZS_MYERS_PACK_QUERIES 1 // 0: one query per workgroup in the fused launch too (the A/B build of query pairs)
+#endif
+#ifndef SZS_MYERS_PAIR_RULES
+#define SZS_MYERS_PAIR_RULES 1 // 0: the sorter always publishes rule 0, slot s with s + ceil(Q / 2) (the A/B build of the pairing rule)
+#endif
 
 #ifndef SZS_MYERS_SHORT_TEXT_DWORDS
 #define SZS_MYERS_SHORT_TEXT_DWORDS 2 // text dwords per main-loop iteration of the short-query bodies: 8 columns (16 left ~7 columns per lane to the predicated tail; measured +1.3 % on config 2)
@@ -358,14 +368,15 @@ __device__ __forceinline__ u64 fused_offset(void const *offsets, u32 wide, u64 i
     return wide ? static_cast<u64 const *>(offsets)[index] : (u64) static_cast<u32 const *>(offsets)[index];
 }
 
-__device__ __forceinline__ void fused_sort_side(szs_plan_side_t const &side, u32 is_query_side, u32 sequence, u32 *ready, u32 second_ready,
-                                                u32 withhold, szs_fused_side_report_t *report, u32 *histogram /* SZS_FUSED_BINS dwords of LDS */,
+__device__ __forceinline__ void fused_sort_side(szs_plan_side_t const &side, u32 is_query_side, u32 choose_rule, u32 sequence, u32 *ready,
+                                                u32 second_ready, u32 withhold, szs_fused_side_report_t *report, u32 *histogram /* SZS_FUSED_BINS dwords of LDS */,
                                                 szs_string_ref_t *staged /* SZS_FUSED_MOST_STRINGS refs of LDS */) {
     constexpr u32 per_thread = SZS_FUSED_MOST_STRINGS / 256;
     u32 const tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, count = side.count;
     bool const one_pass = count <= SZS_FUSED_MOST_STRINGS; // every string of the side in this workgroup's registers at once
     __shared__ u32 wave_bins[4], wave_longest[4], wave_status[4];
     __shared__ unsigned long long wave_symbols[4], wave_bands_systolic[4], wave_bands_chain[4], wave_squares[4];
+    __shared__ u32 rule_words[256];
 
     u64 const began = wall_clock64();
     for (u32 bin = tid; bin < SZS_FUSED_BINS; bin += 256) histogram[bin] = 0;
@@ -465,7 +476,27 @@ __device__ __forceinline__ void fused_sort_side(szs_plan_side_t const &side, u32
             side.ascending[position] = ref, side.descending[count - 1 - position] = ref;
         }
     }
-    else { // ... straight in memory: the second walk over the offsets (they come from the L2 now), sixteen bytes a ref, scattered
+    // ---- the pairing rule (pair_rule.h), while those stores drain: thread t sums the words of candidate t % 17 over every 15th slot
+    //      from t / 17 (the lengths are in LDS, descending rank r at staged[count - 1 - r]) - ~34 slots a thread for 1024 queries
+    u32 const pair_slots = szs_pair_slots(count), pair_seconds = szs_pair_seconds(count);
+    bool const choosing = choose_rule && one_pass && pair_seconds; // uniform; else rule 0
+    if (choosing) {
+        constexpr u32 strides = 256 / SZS_PAIR_RULE_CANDIDATES;
+        // (an opaque copy of the thread's index: what is derived from it is computed HERE - hoisted to the top of the kernel with the
+        // sort's other addresses it cost the scoring bodies a spilled register under their 96)
+        u32 me = tid;
+        asm volatile("" : "+v"(me));
+        u32 const rule = szs_pair_rule_candidate(me % SZS_PAIR_RULE_CANDIDATES, pair_seconds);
+        u32 words = 0;
+        if (me < strides * SZS_PAIR_RULE_CANDIDATES) {
+#pragma unroll 4
+            for (u32 slot = me / SZS_PAIR_RULE_CANDIDATES; slot < pair_seconds; slot += strides)
+                words += szs_pair_slot_words(staged[count - 1 - slot].length,
+                                             staged[count - 1 - szs_pair_second_rank(rule, slot, pair_slots, pair_seconds)].length);
+        }
+        rule_words[me] = words;
+    }
+    if (!one_pass) { // ... straight in memory: the second walk over the offsets (they come from the L2 now), sixteen bytes a ref, scattered
 #pragma unroll 1
         for (u32 first = 0; first < count; first += 1024) {
             u64 some_from[4], some_to[4];
@@ -490,10 +521,32 @@ __device__ __forceinline__ void fused_sort_side(szs_plan_side_t const &side, u32
     // Every thread's stores have reached the L2 behind the barrier (it waits for them; the L1 writes through); ONE agent-scope
     // release by one thread then writes the L2 back before the word that says so changes.
     __syncthreads();
+    if (tid == 0) report->ticks[3] = (u32)(wall_clock64() - began);
+    // the first wavefront folds the 17 totals: the fewest words win, ties go to the lower candidate (rule 0, then the smaller shift)
+    u32 pairing = 0;
+    if (choosing && wave == 0) {
+        constexpr u32 strides = 256 / SZS_PAIR_RULE_CANDIDATES;
+        u32 key = ~0u;
+        if (lane < SZS_PAIR_RULE_CANDIDATES) {
+            u32 total = 0; // at most 512 slots of 16 words: the candidate fits below it
+#pragma unroll
+            for (u32 k = 0; k < strides; ++k) total += rule_words[lane + k * SZS_PAIR_RULE_CANDIDATES];
+            key = (total << 5) | lane;
+        }
+#pragma unroll
+        for (int offset = 16; offset >= 1; offset >>= 1) {
+            u32 const other = (u32)__shfl_xor((int)key, offset, 64);
+            key = other < key ? other : key;
+        }
+        pairing = szs_pair_rule_candidate(key & 31u, pair_seconds);
+    }
     if (tid == 0) {
-        report->ticks[3] = (u32)(wall_clock64() - began);
         if (!withhold) {
-            __hip_atomic_store(ready, sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            // (the query side's word is 64 bits - low half the sequence, high half the rule: ONE store says both, one load reads both)
+            if (is_query_side)
+                __hip_atomic_store(reinterpret_cast<u64 *>(ready), ((u64)pairing << 32) | sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                __hip_atomic_store(ready, sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             if (second_ready) __hip_atomic_store(ready + 32, sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // a symmetric call: both roles
         }
         report->ticks[4] = (u32)(wall_clock64() - began);
@@ -514,7 +567,7 @@ __device__ __forceinline__ void fused_sort_side(szs_plan_side_t const &side, u32
     }
     __syncthreads();
     if (tid == 0) {
-        report->status = status, report->blank = blank, report->reserved = 0;
+        report->status = status, report->blank = blank, report->pairing = pairing;
         report->stats.count = count, report->stats.longest = longest;
         report->stats.symbols = wave_symbols[0] + wave_symbols[1] + wave_symbols[2] + wave_symbols[3];
         report->stats.bands_systolic = wave_bands_systolic[0] + wave_bands_systolic[1] + wave_bands_systolic[2] + wave_bands_systolic[3];
@@ -526,13 +579,13 @@ __device__ __forceinline__ void fused_sort_side(szs_plan_side_t const &side, u32
 
 /** Sorters sort, everybody waits for both sides.  Workgroups are dispatched in order: 0 and 1 never wait for anyone.
  *  False: this workgroup ran out of polls (the sorters are not resident, or one of them never published) - it must not touch a ref. */
-__device__ __forceinline__ bool fused_prologue(szs_fused_plan_t const &plan, u32 *scratch) {
+__device__ __forceinline__ bool fused_prologue(szs_fused_plan_t const &plan, u32 *scratch, u32 &pairing) {
     // 16 KB of LDS that only the two sorting workgroups touch: the scoring bodies keep five workgroups per CU either way (95 VGPRs)
     __shared__ __attribute__((aligned(16))) szs_string_ref_t staged[SZS_FUSED_MOST_STRINGS];
     for (u32 s = 0; s < (plan.symmetric ? 1u : 2u); ++s) // a symmetric call: one side, sorted once, serves both roles
         if (blockIdx.x == s % gridDim.x) {
-            fused_sort_side(plan.side[s], s == 0 || plan.symmetric, plan.sequence, plan.ready + 32 * s, plan.symmetric, plan.withhold, plan.report + s,
-                            scratch, staged);
+            fused_sort_side(plan.side[s], s == 0, SZS_MYERS_PAIR_RULES && SZS_MYERS_PACK_QUERIES && s == 0 && !plan.symmetric && plan.blocks_per_group == 1,
+                            plan.sequence, plan.ready + 32 * s, plan.symmetric, plan.withhold, plan.report + s, scratch, staged);
             __syncthreads(); // the LDS is sorted in again (a grid of one workgroup), then becomes the match masks
         }
     // The wait is a RELAXED load at agent scope (it goes to the device's coherence point every time) and the barrier orders the
@@ -548,16 +601,21 @@ __device__ __forceinline__ bool fused_prologue(szs_fused_plan_t const &plan, u32
     // The wait is BOUNDED (round 6): `poll_budget` polls of ~1 us each, four orders of magnitude beyond what a sorter takes.  A
     // workgroup whose polls run out says so in pinned memory and scores nothing - it leaves the CU to whoever is queued behind it
     // (the sorters, should the dispatch order ever not be the observed one) - and the host plans the call the ordinary way.
-    __shared__ u32 unpublished[2];
+    // The query side's word carries the pairing rule in its high half (pair_rule.h): one 64-bit load reads the sequence and the rule
+    // together, so there is no second word to order behind the first.  (The candidate side's high half is never written.)
+    __shared__ u32 unpublished[2], published_high[2];
     if (threadIdx.x < 2) {
         u32 polls = 0;
+        u64 word;
         bool published;
-        while (!(published = __hip_atomic_load(plan.ready + 32 * threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == plan.sequence) &&
+        while (!(published = (u32)(word = __hip_atomic_load(reinterpret_cast<u64 const *>(plan.ready + 32 * threadIdx.x), __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT)) == plan.sequence) &&
                ++polls < plan.poll_budget)
             __builtin_amdgcn_s_sleep(8);
-        unpublished[threadIdx.x] = !published;
+        unpublished[threadIdx.x] = !published, published_high[threadIdx.x] = (u32)(word >> 32);
     }
     __syncthreads();
+    pairing = (u32)__builtin_amdgcn_readfirstlane((int)published_high[0]); // (uniform: it waits in a scalar register, not in one of every lane's)
     if (unpublished[0] | unpublished[1]) {
         if (threadIdx.x == 0) __hip_atomic_store(plan.gave_up, plan.sequence, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return false;
@@ -568,10 +626,7 @@ __device__ __forceinline__ bool fused_prologue(szs_fused_plan_t const &plan, u32
 #ifndef SZS_MYERS_SHORT_WAVES
 #define SZS_MYERS_SHORT_WAVES 1
 #endif
-#ifndef SZS_MYERS_PACK_QUERIES
-#define SZS_MYERS_PACK_QUERIES 1 // 0: one query per workgroup in the fused launch too (the A/B build of query pairs)
-#endif
-constexpr u32 szs_myers_pair_words_k = 10; // the widest bit-vector of two queries: config 2's pairs take 8 to 10 words
+constexpr u32 szs_myers_pair_words_k = SZS_PAIR_WORDS_MOST; // the widest bit-vector of two queries: config 2's pairs take 8 to 10 words
 /**
  *  Short queries (up to 256 symbols = 8 words), ANY mix of lengths in ONE launch: the width is a per-workgroup (scalar)
  *  decision, so every query runs at exactly ceil(length / 32) words, and a batch whose queries straddle several widths
@@ -585,9 +640,10 @@ __device__ __forceinline__ void myers_short_body(
     u32 blocks_per_group, szs_fused_plan_t const *fused = nullptr) {
     constexpr bool pairs = fused_ && !merged_ && SZS_MYERS_PACK_QUERIES; // (a pair of queries takes up to szs_myers_pair_words_k words)
     __shared__ __attribute__((aligned(16))) u32 peq[peq_layout<pairs ? szs_myers_pair_words_k : 8, runes_ ? rune_slots_k : byte_rows_k>::total_dwords];
+    u32 pairing = 0; // the rule the query side's sorter published (pair_rule.h)
     if constexpr (fused_) {
         static_assert(peq_layout<8, byte_rows_k>::total_dwords >= SZS_FUSED_BINS, "the sort's histogram borrows the masks' LDS");
-        if (!fused_prologue(*fused, peq)) return; // the refs `queries` / `candidates` point at exist from here on
+        if (!fused_prologue(*fused, peq, pairing)) return; // the refs `queries` / `candidates` point at exist from here on
     }
     __shared__ u32 slot_keys[runes_ ? rune_slots_k : 1];
     __shared__ u32 claimed_rows;
@@ -614,15 +670,18 @@ __device__ __forceinline__ void myers_short_body(
         query.index = (u32)__builtin_amdgcn_readfirstlane((int)query.index);
     }
     // Query pairs (fused byte launches of one block per workgroup, non-symmetric): slot s of the ceil(Q / 2) slots scores the
-    // descending refs s and s + ceil(Q / 2) - in one bit-vector when that takes no more words than the two apart and at most
-    // szs_myers_pair_words_k, one after the other otherwise (and alone: the middle query of an odd count).
+    // descending ref s and the one the published rule gives it (pair_rule.h: s + ceil(Q / 2) under rule 0) - in one bit-vector when
+    // that takes no more words than the two apart and at most szs_myers_pair_words_k, one after the other otherwise (and alone:
+    // the middle query of an odd count).
     szs_string_ref_t second = {0, 0, 0};
     bool has_second = false;
     if constexpr (pairs) {
         if (!fused->symmetric) {
-            u32 const slots = (fused->side[0].count + 1u) / 2u;
-            if (query_slot + slots < fused->side[0].count) {
-                second = queries[query_slot + slots];
+            u32 const slots = szs_pair_slots(fused->side[0].count), seconds = szs_pair_seconds(fused->side[0].count);
+            if (query_slot < seconds) {
+                u32 rule = pairing;
+                rule = rule <= seconds ? rule : 0u; // (what the rank below requires: no word of memory can send a read out of the refs)
+                second = queries[szs_pair_second_rank(rule, query_slot, slots, seconds)];
                 second.address = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(second.address >> 32)) << 32) |
                                  (u32)__builtin_amdgcn_readfirstlane((int)(u32)second.address);
                 second.length = (u32)__builtin_amdgcn_readfirstlane((int)second.length);
@@ -633,9 +692,9 @@ __device__ __forceinline__ void myers_short_body(
     }
     u32 const words = __builtin_amdgcn_readfirstlane(query.length ? (query.length + 31u) / 32u : 1u);
     u32 const second_words = second.length ? (second.length + 31u) / 32u : 1u;
-    u32 const pair_words = (query.length + second.length + 2u + 31u) / 32u;
+    u32 const pair_words = szs_pair_words_shared(query.length, second.length);
     if constexpr (pairs) {
-        if (has_second && pair_words <= words + second_words && pair_words <= szs_myers_pair_words_k) {
+        if (has_second && szs_pair_shares(pair_words, words, second_words)) {
 #define SZS_MYERS_PAIR_BODY(W)                                                                                         \
     case W:                                                                                                            \
         myers_workgroup<W, SZS_MYERS_SHORT_TEXT_DWORDS, false, true>(peq, keys, query, candidates, candidates_count,   \

@@ -1225,6 +1225,7 @@ sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input
     size_t const candidates_count = symmetric ? queries_count : candidates->count;
     engine->cells_before = engine->last_profile.cells;
     memset(&engine->last_profile, 0, sizeof(engine->last_profile));
+    engine->last_pairing = 0;
     /* The dense byte alphabet of a non-unit Levenshtein engine belongs to ONE call: only the device-planned path scans the
      * tapes and fills it, and szs_call_decide() / fill_cost_model() read it on every path - a host-planned call after a device-planned
      * one must not score with the previous batch's byte-to-class map (bytes that batch lacked would all share class 0). */

@@ -65,11 +65,13 @@ _Static_assert(sizeof(szs_pinned_words_t) <= SZS_PINNED_WORDS_BYTES, "the pinned
 
 /** engine->device_fused: device memory, zeroed when allocated and after a failed call, never by a launch (szs_call_reserve_device_words). */
 typedef struct szs_device_words_t {
-    uint32_t ready[48];   /* the launch that plans itself: ready[0] and ready[32], one word a side (szs_fused_plan_t) */
+    uint32_t ready[48];   /* the launch that plans itself: ready[0] and ready[32], one word a side (szs_fused_plan_t); ready[0 .. 1] are
+                             ONE 64-bit word - the sequence below, the query side's pairing rule above */
     uint32_t verdicts[8]; /* the two-workgroup planner's (szs_hip_plan) */
     uint32_t unused[8];
 } szs_device_words_t;
 _Static_assert(offsetof(szs_device_words_t, verdicts) == 48 * sizeof(uint32_t) && sizeof(szs_device_words_t) == 256, "device words moved");
+_Static_assert(offsetof(szs_device_words_t, ready) % 8 == 0, "the query side's ready word is read as 64 bits");
 
 static inline szs_pinned_words_t volatile *szs_pinned_words(szs_engine_s const *engine) {
     return (szs_pinned_words_t volatile *)engine->pinned_summary.pointer;

@@ -7,6 +7,7 @@
  *  GPU engines only, so `capabilities` must contain sz_cap_cuda_k.
  */
 #include "szs_internal.h"
+#include "../hip/pair_rule.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -260,6 +261,49 @@ sz_status_t szs_rocm_last_call_profile(void *handle, szs_rocm_call_profile_t *pr
     szs_engine_s *engine = (szs_engine_s *)handle;
     if (!engine || engine->magic != SZS_ENGINE_MAGIC || !profile) return sz_status_unknown_k;
     *profile = engine->last_profile;
+    return sz_success_k;
+}
+
+sz_u32_t szs_rocm_last_pairing(void *handle) {
+    szs_engine_s const *engine = (szs_engine_s const *)handle;
+    return engine && engine->magic == SZS_ENGINE_MAGIC ? engine->last_pairing : 0u;
+}
+
+static int descending_lengths(void const *a, void const *b) {
+    sz_u32_t const x = *(sz_u32_t const *)a, y = *(sz_u32_t const *)b;
+    return x < y ? 1 : x > y ? -1 : 0;
+}
+
+/* The choice of fused_sort_side (hip/lev_myers.hip) on bare lengths, through the same header. */
+sz_status_t szs_rocm_pair_rule_probe(sz_u32_t const *lengths, sz_size_t count, sz_u32_t *rule, sz_u64_t *total_words, sz_u32_t *slot_pairs_out) {
+    if (!rule || (count && !lengths) || count > 0x7FFFFFFFull) return sz_status_unknown_k;
+    unsigned const queries = (unsigned)count, slots = szs_pair_slots(queries), seconds = szs_pair_seconds(queries);
+    if (*rule != SZS_ROCM_PAIR_RULE_CHOOSE && *rule > seconds) return sz_unexpected_dimensions_k;
+    sz_u32_t *const ranked = (sz_u32_t *)malloc((count ? count : 1) * sizeof(sz_u32_t));
+    if (!ranked) return sz_bad_alloc_k;
+    int blank = 0; /* a query beyond the short kernel: the sorter writes every length as 0 and the host plans the call another way */
+    for (unsigned i = 0; i < queries; ++i) ranked[i] = lengths[i], blank |= lengths[i] > 32u * SZS_MYERS_SHORT_WORDS;
+    if (blank) memset(ranked, 0, count * sizeof(sz_u32_t));
+    qsort(ranked, count, sizeof(sz_u32_t), descending_lengths);
+    sz_u64_t alone = 0; /* the middle query of an odd count: the same under every rule */
+    for (unsigned slot = seconds; slot < slots; ++slot) alone += szs_pair_words_alone(ranked[slot]);
+    unsigned chosen = *rule == SZS_ROCM_PAIR_RULE_CHOOSE ? 0u : *rule;
+    sz_u64_t fewest = 0;
+    for (unsigned k = 0; k < (*rule == SZS_ROCM_PAIR_RULE_CHOOSE ? SZS_PAIR_RULE_CANDIDATES : 1u); ++k) {
+        unsigned const candidate = *rule == SZS_ROCM_PAIR_RULE_CHOOSE ? szs_pair_rule_candidate(k, seconds) : *rule;
+        if (k && (!seconds || queries > SZS_FUSED_MOST_STRINGS)) break; /* larger sides are not staged in LDS: rule 0 */
+        sz_u64_t words = alone;
+        for (unsigned slot = 0; slot < seconds; ++slot)
+            words += szs_pair_slot_words(ranked[slot], ranked[szs_pair_second_rank(candidate, slot, slots, seconds)]);
+        if (!k || words < fewest) fewest = words, chosen = candidate;
+    }
+    *rule = chosen;
+    if (total_words) *total_words = fewest;
+    if (slot_pairs_out)
+        for (unsigned slot = 0; slot < slots; ++slot)
+            slot_pairs_out[2 * slot] = slot,
+                               slot_pairs_out[2 * slot + 1] = slot < seconds ? szs_pair_second_rank(chosen, slot, slots, seconds) : 0xFFFFFFFFu;
+    free(ranked);
     return sz_success_k;
 }
 

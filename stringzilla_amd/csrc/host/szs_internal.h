@@ -126,6 +126,7 @@ typedef struct szs_engine_s {
                                       (dispatch_internal.h: szs_device_words_t) */
     void *fused_zeroed;            /* the allocation of `device_fused` that was zeroed */
     int fused_gave_up;             /* a launch that plans itself ran out of polls on this engine: it is not tried again */
+    uint32_t last_pairing;         /* the pairing rule the last call's query sorter published (hip/pair_rule.h); 0 also when no launch planned itself */
     szs_tiny_memory_t tiny[2];     /* [0] byte calls, [1] codepoint calls (narrowed to byte strings of rune ids, then that kernel) */
     int tiny_refused;              /* the kernel REFUSED a batch of tiny[0]'s counts (dense in long strings): calls of these counts skip the
                                       summary-driven attempt while this counts down - whichever family refused */

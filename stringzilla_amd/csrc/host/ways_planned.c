@@ -253,13 +253,14 @@ static sz_status_t planned_inside_the_launch(planned_call_t *way) {
     if (!(sides[0].sequence == fused.sequence && !sides[0].status && !sides[0].blank &&
           (symmetric || (sides[1].sequence == fused.sequence && !sides[1].status && !sides[1].blank))))
         return SZS_WAY_NOT_TAKEN; /* not this shape after all: nothing real was scored */
+    engine->last_pairing = sides[0].pairing; /* of the KERNEL's query side */
     /* scored; the profile and the remembered plan take this batch's figures (caller roles again; a symmetric call has one side) */
     szs_fused_side_report_t const *const of_queries = &sides[!symmetric && d->transposed ? 1 : 0];
     szs_fused_side_report_t const *const of_candidates = symmetric ? of_queries : &sides[d->transposed ? 0 : 1];
     if (call->trace)
         for (int s = 0; s < (symmetric ? 1 : 2); ++s)
-            fprintf(stderr, "fused sorter %d (10 ns ticks since it began): offsets loaded %u, positions %u, refs written %u, published %u; began %d ticks after sorter 0\n",
-                    s, sides[s].ticks[1], sides[s].ticks[2], sides[s].ticks[3], sides[s].ticks[4], (int)(sides[s].ticks[0] - sides[0].ticks[0]));
+            fprintf(stderr, "fused sorter %d (10 ns ticks since it began): offsets loaded %u, positions %u, refs written %u, published %u; began %d ticks after sorter 0; pairing rule %u\n",
+                    s, sides[s].ticks[1], sides[s].ticks[2], sides[s].ticks[3], sides[s].ticks[4], (int)(sides[s].ticks[0] - sides[0].ticks[0]), sides[s].pairing);
     szs_plan_summary_t seen_here = remembered->summary;
     seen_here.status = 0, seen_here.speculation_held = 1, seen_here.sequence = fused.sequence;
     seen_here.side[0] = of_queries->stats, seen_here.side[1] = of_candidates->stats;
