@@ -18,6 +18,8 @@
  *  - szs_rocm_top_k*            : the k best candidates of every query, without the queries x candidates matrix (csrc/host/top_k.c).
  *  - szs_rocm_rerank*           : exact scores of LISTED candidates per query - what verifies the hits of a coarse search (top-k's own
  *    `indices`, a fingerprint search, any outside candidate generator) without a queries x candidates matrix (csrc/host/rerank.c).
+ *  - szs_rocm_fuzzy_find*       : the best match of a query INSIDE each listed candidate - fewest edits to some substring, and where it
+ *    ends - for a snippet in a document, a primer in a read, a misspelled name in a record (csrc/host/fuzzy_find.c).
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -158,6 +160,50 @@ SZ_API_RUNTIME sz_status_t szs_rocm_rerank_u32tape(void *engine, szs_device_scop
 SZ_API_RUNTIME sz_status_t szs_rocm_rerank_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
                                                    sz_sequence_u64tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
                                                    void *scores, sz_size_t row_stride, char const **error_message);
+
+/**
+ *  Fuzzy substring search: where inside a candidate does something close to the query occur, and how close?  For a query q of m
+ *  bytes and a candidate c of n bytes let D be the unit-cost DP with a FREE START in the text: D[0][j] = 0, D[i][0] = i,
+ *  D[i][j] = min(D[i-1][j-1] + (q[i-1] != c[j-1]), D[i-1][j] + 1, D[i][j-1] + 1).  Per pair the call writes
+ *      distances[q * row_stride + r] = min over j in [0, n] of D[m][j]  - the fewest edits that turn q into SOME substring of c: at
+ *                                      most m, and at most the global distance;
+ *      ends[q * row_stride + r]      = the smallest j that attains it   - the exclusive byte offset in c at which the leftmost-ending
+ *                                      best match ends; 0: the empty substring (distance m).
+ *  Start offsets are not reported.  `ends` may be NULL, `distances` may not.
+ *
+ *  Rows and slots are szs_rocm_rerank's: `indices`, `distances` and `ends` share `row_stride`, in 8-byte cells; slot r of row q pairs
+ *  queries[q] with candidates[indices[q * row_stride + r]] for r < k; cells [k, row_stride) are left untouched; k >= 1 and
+ *  row_stride >= k, else sz_unexpected_dimensions_k.  An index of SZ_SIZE_MAX is an empty slot: distance 0, end 0, no string
+ *  touched.  Any other index >= the candidates' count fails the whole call with sz_unexpected_dimensions_k and addresses nothing:
+ *  indices the host can read are validated before anything is launched, indices only the device can read are checked by the kernel
+ *  before every use.  After a failed call the contents of the outputs are unspecified.
+ *  `indices` NULL is the DENSE form - every query in every candidate, without a queries x candidates index matrix: slot r is
+ *  candidate r, and k must equal the candidates' count, else sz_unexpected_dimensions_k.
+ *  `candidates` NULL: the indices refer to `queries` themselves; no index is excluded.
+ *
+ *  TWO LIMITS.  (1) `engine` must be a unit-cost BYTE Levenshtein engine (szs_levenshtein_distances_init with match 0, mismatch 1,
+ *  open 1, extend 1): any other engine - other costs, UTF-8 codepoints, Needleman-Wunsch, Smith-Waterman - and a blank or NULL one is
+ *  refused with sz_status_unknown_k and a message, and nothing is written.  (2) Every query has at most 256 bytes: a longer one fails
+ *  the whole call with sz_unexpected_dimensions_k.  Candidates may have any length below 4 GiB.  There is no slower route behind
+ *  either limit: no engine call computes this distance.
+ *
+ *  Zero queries: success, nothing written.  `indices`, the outputs and the strings' offsets may live in host, pinned, unified or
+ *  device memory; the strings themselves must be readable by the device.  The call runs on the scope's stream and is synchronous,
+ *  also when it fails.  All rows of up to 2^20 queries are ONE launch (csrc/hip/myers_fuzzy_find.hip).
+ *  szs_rocm_last_call_profile reports the sums over the call: pairs (non-empty slots), cells (m x n over them), kernel time,
+ *  launches, wall time.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                               sz_sequence_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                               sz_size_t *distances, sz_size_t *ends, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                       sz_sequence_u32tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                       sz_size_t *distances, sz_size_t *ends, sz_size_t row_stride,
+                                                       char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                       sz_sequence_u64tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                       sz_size_t *distances, sz_size_t *ends, sz_size_t row_stride,
+                                                       char const **error_message);
 
 /**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine

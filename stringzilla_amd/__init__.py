@@ -226,6 +226,26 @@ def _as_strs(collection) -> Strs:
     return collection if isinstance(collection, Strs) else Strs(collection)
 
 
+def _listed_cells(matrix, name, shape_wanted):
+    """A `(rows, k)` matrix of 8-byte cells with contiguous rows, as `rerank` and `fuzzy_find` take them -> (pointer, row stride in
+    cells, shape); ValueError otherwise."""
+    import torch
+
+    if isinstance(matrix, np.ndarray):
+        shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
+        pointer, whole = matrix.ctypes.data, all(s % 8 == 0 for s in matrix.strides)
+    elif type(matrix).__module__.partition(".")[0] == "torch" and hasattr(matrix, "data_ptr"):
+        shape, itemsize, strides, pointer, whole = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr(), True
+        if matrix.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
+            torch.cuda.current_stream(matrix.device).synchronize()
+    else:
+        raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(matrix).__name__}")
+    if len(shape) != 2 or shape[1] < 1 or (shape_wanted is not None and shape != shape_wanted) or itemsize != 8 or not whole or (
+            shape[1] > 1 and strides[1] != 1) or (shape[0] > 1 and strides[0] < shape[1]):
+        raise ValueError(f"`{name}` must be a (rows, k) matrix of 8-byte cells with contiguous rows, k at least 1")
+    return pointer, strides[0] if shape[0] > 1 else shape[1], shape
+
+
 class _Engine:
     """Shared call path: `engine(queries, candidates=None, device=None, out=None)` (README.md:472-482)."""
 
@@ -362,28 +382,13 @@ class _Engine:
         NumPy array or torch tensor of 8-byte cells that shares the row stride of `indices`)."""
         import torch
 
-        def cells_of(matrix, name, shape_wanted):  # -> (pointer, row stride in cells, shape)
-            if isinstance(matrix, np.ndarray):
-                shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
-                pointer, whole = matrix.ctypes.data, all(s % 8 == 0 for s in matrix.strides)
-            elif type(matrix).__module__.partition(".")[0] == "torch" and hasattr(matrix, "data_ptr"):
-                shape, itemsize, strides, pointer, whole = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr(), True
-                if matrix.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
-                    torch.cuda.current_stream(matrix.device).synchronize()
-            else:
-                raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(matrix).__name__}")
-            if len(shape) != 2 or shape[1] < 1 or (shape_wanted is not None and shape != shape_wanted) or itemsize != 8 or not whole or (
-                    shape[1] > 1 and strides[1] != 1) or (shape[0] > 1 and strides[0] < shape[1]):
-                raise ValueError(f"`{name}` must be a (rows, k) matrix of 8-byte cells with contiguous rows, k at least 1")
-            return pointer, strides[0] if shape[0] > 1 else shape[1], shape
-
         queries = _as_strs(queries)
         candidates = None if candidates is None else _as_strs(candidates)
-        indices_pointer, stride, (rows, k) = cells_of(indices, "indices", None)
+        indices_pointer, stride, (rows, k) = _listed_cells(indices, "indices", None)
         if rows != len(queries):
             raise ValueError(f"`indices` must have one row per query: {rows} rows, {len(queries)} queries")
         if out is not None:
-            scores_pointer, scores_stride, _ = cells_of(out, "out", (rows, k))
+            scores_pointer, scores_stride, _ = _listed_cells(out, "out", (rows, k))
             if scores_stride != stride:
                 raise ValueError("`out` and `indices` must share one row stride")
         scope = device or self._scope or _get_default_scope()
@@ -412,6 +417,67 @@ class _Engine:
             return out
         host = results[:rows].cpu().numpy() if stride == k else results[:rows, :k]
         return host.view(self._dtype)
+
+    def fuzzy_find(self, queries, candidates, indices=None, device: Optional[DeviceScope] = None, out=None):
+        """The best match of every query INSIDE the candidates listed for it (`szs_rocm_fuzzy_find_*`): returns `(distances, ends)`,
+        two `uint64` `(rows, k)` NumPy matrices - `distances[q, r]` is the fewest edits that turn `queries[q]` into some substring of
+        `candidates[indices[q, r]]`, `ends[q, r]` the smallest exclusive byte offset at which such a substring ends (0: the empty one).
+        `indices` is what `rerank` takes; None is the dense form, every query in every candidate: the results are
+        `(rows, len(candidates))`.  `candidates` None: the indices refer to `queries` (and must be given).  2**64 - 1 marks an empty
+        slot (0, 0).  `out`: a pair of NumPy arrays or torch tensors of 8-byte cells that share the row stride of `indices`, filled
+        and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes."""
+        import torch
+
+        queries = _as_strs(queries)
+        candidates = None if candidates is None else _as_strs(candidates)
+        rows = len(queries)
+        if indices is None:
+            if candidates is None or len(candidates) < 1:
+                raise ValueError("`indices` None needs at least one candidate; `candidates` None needs `indices`")
+            indices_pointer, k, stride = None, len(candidates), None
+        else:
+            indices_pointer, stride, (index_rows, k) = _listed_cells(indices, "indices", None)
+            if index_rows != rows:
+                raise ValueError(f"`indices` must have one row per query: {index_rows} rows, {rows} queries")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise ValueError("`out` must be a pair (distances, ends)")
+            pointers = []
+            for matrix, name in zip(out, ("out distances", "out ends")):
+                pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
+                if stride is not None and own_stride != stride:
+                    raise ValueError("`out` and `indices` must share one row stride")
+                stride = own_stride
+                pointers.append(pointer)
+            distances_pointer, ends_pointer = pointers
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        for matrix, name in ((indices, "indices"),) + (tuple(zip(out, ("out distances", "out ends"))) if out is not None else ()):
+            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
+                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
+        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
+            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        if out is None:
+            if stride is None or stride == k:
+                stride = k
+                results = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+                distances_pointer, ends_pointer = results[0].data_ptr(), results[1].data_ptr()
+            else:  # the outputs share the stride of the indices: host matrices as wide as theirs
+                results = np.zeros((2, max(rows, 1), stride), dtype=np.int64)
+                distances_pointer, ends_pointer = results[0].ctypes.data, results[1].ctypes.data
+
+        error = ctypes.c_char_p()
+        call = lib.szs_rocm_fuzzy_find_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_find_u32tape
+        q_tape = queries._tape(gpu_device)
+        c_tape = None if candidates is None else candidates._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
+                      indices_pointer, k, distances_pointer, ends_pointer, stride, ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        host = results[:, :rows].cpu().numpy() if isinstance(results, torch.Tensor) else results[:, :rows, :k]
+        return host[0].view(np.uint64), host[1].view(np.uint64)
 
     def __del__(self):
         handle = getattr(self, "handle", None)

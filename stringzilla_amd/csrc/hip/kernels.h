@@ -319,6 +319,18 @@ int szs_hip_levenshtein_rerank_strips(szs_rerank_side_t const *queries, szs_rera
                                       uint64_t k, uint64_t *scores, uint64_t scores_stride, uint32_t workgroups, uint32_t *parked,
                                       uint32_t parked_dwords, uint32_t *flags, unsigned long long *counters, void *stream);
 
+/**
+ *  Fuzzy find (hip/myers_fuzzy_find.hip; host/fuzzy_find.c): the best match of a query INSIDE each listed
+ *  candidate - distances[row * outputs_stride + r] = the fewest edits that turn the query into some substring of the candidate, and
+ *  (`ends` not NULL) ends[...] = the smallest exclusive byte offset in the candidate at which such a substring ends.  Rows, groups,
+ *  sides, `widest`, flags and counters are szs_hip_levenshtein_rerank's; `indices` NULL: slot r is candidate r.  An empty slot
+ *  receives distance 0 and end 0.
+ */
+int szs_hip_levenshtein_fuzzy_find(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,
+                                   uint32_t const *rows, uint32_t rows_count, uint64_t const *indices, uint64_t indices_stride,
+                                   uint64_t k, uint64_t *distances, uint64_t *ends, uint64_t outputs_stride, unsigned widest,
+                                   uint32_t *flags, unsigned long long *counters, void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {

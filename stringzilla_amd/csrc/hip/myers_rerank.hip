@@ -155,16 +155,6 @@ __global__ __launch_bounds__(64) void levenshtein_rerank_kernel(szs_rerank_side_
 #undef SZS_RERANK_BODY
 }
 
-static u32 rerank_table_dwords(unsigned widest) {
-    switch (widest) {
-    case 1: return peq_layout<1>::total_dwords;
-    case 2: return peq_layout<2>::total_dwords;
-    case 3:
-    case 4: return peq_layout<4>::total_dwords;
-    default: return peq_layout<8>::total_dwords;
-    }
-}
-
 } // namespace szs_hip
 
 extern "C" unsigned szs_hip_rerank_lanes(uint64_t k) { return k <= 16 ? 16u : k <= 32 ? 32u : 64u; }

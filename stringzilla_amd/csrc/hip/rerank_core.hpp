@@ -1,6 +1,6 @@
 /*
  *  rerank_core.hpp - what the two rerank kernels share (hip/myers_rerank.hip: queries of up to 256 bytes in one bit-vector;
- *  hip/myers_rerank_strips.hip: longer queries as strips): the fetch of a string through an index, the phantom-row mask of a
+ *  hip/myers_rerank_strips.hip: longer queries as strips) and the fuzzy-find kernel (hip/myers_fuzzy_find.hip): the fetch of a string through an index, the phantom-row mask of a
  *  word, the wavefront sum of the counters.
  */
 #pragma once
@@ -34,6 +34,18 @@ __device__ __forceinline__ bool rerank_fetch(szs_rerank_side_t const &side, u64 
     if (to < from || to - from > 0xFFFFFFFFull) return false;
     address = side.base + from, length = (u32)(to - from);
     return true;
+}
+
+/** Dwords of one row's Peq table in a launch whose widest query needs `widest` words (a table of W words fits the table of the next
+ *  even chunk count): what the one-strip kernels size their dynamic LDS by. */
+inline u32 rerank_table_dwords(unsigned widest) {
+    switch (widest) {
+    case 1: return peq_layout<1>::total_dwords;
+    case 2: return peq_layout<2>::total_dwords;
+    case 3:
+    case 4: return peq_layout<4>::total_dwords;
+    default: return peq_layout<8>::total_dwords;
+    }
 }
 
 __device__ __forceinline__ u64 wave_sum_u64(u64 value) {

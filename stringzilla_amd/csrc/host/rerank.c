@@ -22,25 +22,13 @@
  *  most one launch of each kernel, the scores home), rerank_row (the row route).  The routes write disjoint rows of `scores`, so none
  *  depends on running before another.  szs_rocm_rerank_probe reports the routing of bare lengths through the same functions.
  */
-#include "szs_internal.h"
+#include "rerank_internal.h"
 
-#include <string.h>
-#include <time.h>
-
-#define SZS_RERANK_STAGE_BYTES ((size_t)128 << 20) /* a block's dense copy of indices or scores the device cannot reach */
-#define SZS_RERANK_MOST_ROWS ((size_t)1 << 20)     /* rows of a block: bounds the kernel's row list */
-#define SZS_RERANK_EMPTY (~(uint64_t)0)            /* SZ_SIZE_MAX: the empty slot top-k emits */
 #define SZS_RERANK_PARKED_BYTES ((size_t)256 << 20) /* the parked deltas of the strips launch: a chosen budget (what top-k and the
                                                        fingerprint search give their staging), not a measurement */
 #define SZS_RERANK_STRIPS_TABLES 5120u             /* 8 KB tables that 256 CUs x 160 KB of LDS hold: the most rows in flight */
 
 enum { szs_rerank_route_row_k = 0, szs_rerank_route_kernel_k = 1, szs_rerank_route_strips_k = 2 };
-
-static double now_milliseconds(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
 
 /* ---- gathered sequences: strings picks[0 .. count) of a side, for the row route ------------------------------------------- */
 
@@ -51,20 +39,17 @@ typedef struct {
     uint64_t const *picks;
 } szs_gathered_sequence_t;
 
-static uint64_t tape_offset(szs_input_t const *input, void const *offsets, size_t i) {
-    return input->kind == szs_input_u32tape_k ? ((uint32_t const *)offsets)[i] : ((uint64_t const *)offsets)[i];
-}
 static sz_cptr_t gathered_start(void const *handle, sz_sorted_idx_t i) {
     szs_gathered_sequence_t const *gathered = (szs_gathered_sequence_t const *)handle;
     size_t const at = (size_t)gathered->picks[i];
     if (gathered->base->kind == szs_input_sequence_k) return gathered->base->sequence->get_start(gathered->base->sequence->handle, at);
-    return gathered->base->data + tape_offset(gathered->base, gathered->offsets, at);
+    return gathered->base->data + szs_tape_offset(gathered->base, gathered->offsets, at);
 }
 static sz_size_t gathered_length(void const *handle, sz_sorted_idx_t i) {
     szs_gathered_sequence_t const *gathered = (szs_gathered_sequence_t const *)handle;
     size_t const at = (size_t)gathered->picks[i];
     if (gathered->base->kind == szs_input_sequence_k) return gathered->base->sequence->get_length(gathered->base->sequence->handle, at);
-    uint64_t const from = tape_offset(gathered->base, gathered->offsets, at), to = tape_offset(gathered->base, gathered->offsets, at + 1);
+    uint64_t const from = szs_tape_offset(gathered->base, gathered->offsets, at), to = szs_tape_offset(gathered->base, gathered->offsets, at + 1);
     return to >= from ? to - from : SZS_RERANK_EMPTY; /* descending offsets: a length no call accepts */
 }
 static szs_input_t gather_input(szs_input_t const *base, void const *offsets, uint64_t const *picks, size_t count,
@@ -76,67 +61,12 @@ static szs_input_t gather_input(szs_input_t const *base, void const *offsets, ui
     return input;
 }
 
-/** The offsets of a tape where the host can read them: as they are, or copied to the host - once per call. */
-static sz_status_t host_offsets_of(szs_input_t const *input, szs_buffer_t *copy, hipStream_t stream, void const **offsets,
-                                   char const **error_message) {
-    *offsets = input->offsets;
-    if (input->kind == szs_input_sequence_k) return sz_success_k;
-    if (!input->offsets) return szs_report(sz_status_unknown_k, error_message, "Tape offsets must not be null");
-    if (szs_classify_pointer(input->offsets).host_readable) return sz_success_k;
-    size_t const bytes = (input->count + 1) * (input->kind == szs_input_u32tape_k ? 4 : 8);
-    sz_status_t const status = szs_buffer_reserve(copy, szs_memory_host_k, 0, bytes, error_message);
-    if (status != sz_success_k) return status;
-    hipError_t error = hipMemcpyAsync(copy->pointer, input->offsets, bytes, hipMemcpyDeviceToHost, stream);
-    if (error == hipSuccess) error = hipStreamSynchronize(stream);
-    if (error != hipSuccess) return szs_report_hip(error, error_message);
-    *offsets = copy->pointer;
-    return sz_success_k;
-}
-
-static size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-/** A side does not need refs when it is a tape whose offsets the device reads itself. */
-static int side_needs_refs(szs_input_t const *input) {
-    return input->kind == szs_input_sequence_k || !szs_classify_pointer(input->offsets).device_accessible;
-}
-
-/**
- *  One side as the kernel reads it: the tape itself, or refs in index order built on the host and uploaded.  `*usable` 0: the kernel
- *  cannot reach the side's strings (or its offsets are malformed) - every row then takes the row route, which reports what is wrong.
- */
-static sz_status_t kernel_side(szs_input_t const *input, void const *offsets, int needs_refs, uint64_t *addresses, uint32_t *lengths,
-                               szs_string_ref_t *pinned_refs, szs_string_ref_t *device_refs, hipStream_t stream, szs_rerank_side_t *side,
-                               int *usable, char const **error_message) {
-    memset(side, 0, sizeof(*side));
-    side->count = input->count, *usable = 1;
-    if (!needs_refs) {
-        side->offsets = input->offsets, side->base = (uint64_t)(uintptr_t)input->data, side->wide = input->kind == szs_input_u64tape_k;
-        uint64_t const bytes = tape_offset(input, offsets, input->count) - tape_offset(input, offsets, 0);
-        *usable = !bytes || szs_classify_pointer(input->data).device_accessible;
-        return sz_success_k;
-    }
-    char const *ignored = NULL;
-    uint64_t bytes = 0;
-    if (szs_gather_strings(input, offsets, addresses, lengths, &bytes, NULL, &ignored) != sz_success_k) {
-        *usable = 0;
-        return sz_success_k;
-    }
-    for (size_t i = 0; i < input->count; ++i)
-        pinned_refs[i].address = addresses[i], pinned_refs[i].length = lengths[i], pinned_refs[i].index = (uint32_t)i;
-    side->refs = device_refs;
-    if (!input->count) return sz_success_k;
-    hipError_t const error = hipMemcpyAsync(device_refs, pinned_refs, input->count * sizeof(szs_string_ref_t), hipMemcpyHostToDevice, stream);
-    return error == hipSuccess ? sz_success_k : szs_report_hip(error, error_message);
-}
-
 static void add_profile(szs_rocm_call_profile_t *total, szs_rocm_call_profile_t const *part) {
     total->kernel_milliseconds += part->kernel_milliseconds, total->cells += part->cells, total->pairs += part->pairs;
     total->algorithmic_bytes += part->algorithmic_bytes, total->unique_bytes += part->unique_bytes, total->launches += part->launches;
     if (part->longest_query > total->longest_query) total->longest_query = part->longest_query;
     if (part->longest_candidate > total->longest_candidate) total->longest_candidate = part->longest_candidate;
 }
-
-static int index_is_bad(uint64_t index, size_t count) { return index != SZS_RERANK_EMPTY && index >= count; }
 
 /* ---- scratch layouts ------------------------------------------------------------------------------------------------------ */
 
@@ -164,31 +94,25 @@ typedef struct {
     size_t device_bytes;
 } szs_rerank_layout_t;
 
-static size_t layout_part(size_t *end, size_t bytes) {
-    size_t const at = *end;
-    *end = at + align16(bytes);
-    return at;
-}
-
 static szs_rerank_layout_t rerank_layout(size_t q_count, size_t gathered, size_t block, size_t k, int indices_on_host, size_t refs_total) {
     szs_rerank_layout_t layout;
     size_t end = 0;
-    layout.host_query_lengths = layout_part(&end, q_count * sizeof(uint32_t));
-    layout.host_addresses = layout_part(&end, gathered * sizeof(uint64_t));
-    layout.host_gathered_lengths = layout_part(&end, gathered * sizeof(uint32_t));
-    layout.host_indices = layout_part(&end, indices_on_host ? 0 : block * k * sizeof(uint64_t));
-    layout.host_picks = layout_part(&end, k * sizeof(uint64_t));
+    layout.host_query_lengths = szs_layout_part(&end, q_count * sizeof(uint32_t));
+    layout.host_addresses = szs_layout_part(&end, gathered * sizeof(uint64_t));
+    layout.host_gathered_lengths = szs_layout_part(&end, gathered * sizeof(uint32_t));
+    layout.host_indices = szs_layout_part(&end, indices_on_host ? 0 : block * k * sizeof(uint64_t));
+    layout.host_picks = szs_layout_part(&end, k * sizeof(uint64_t));
     layout.host_bytes = end, end = 0;
-    layout.pinned_flags = layout_part(&end, SZS_RERANK_FLAGS * sizeof(uint32_t));
-    layout.pinned_landed = layout_part(&end, 3 * sizeof(uint64_t));
-    layout.pinned_cells = layout_part(&end, k * sizeof(uint64_t));
-    layout.pinned_image = layout_part(&end, k * sizeof(uint64_t));
-    layout.pinned_rows = layout_part(&end, block * sizeof(uint32_t));
-    layout.pinned_refs = layout_part(&end, refs_total * sizeof(szs_string_ref_t));
+    layout.pinned_flags = szs_layout_part(&end, SZS_RERANK_FLAGS * sizeof(uint32_t));
+    layout.pinned_landed = szs_layout_part(&end, 3 * sizeof(uint64_t));
+    layout.pinned_cells = szs_layout_part(&end, k * sizeof(uint64_t));
+    layout.pinned_image = szs_layout_part(&end, k * sizeof(uint64_t));
+    layout.pinned_rows = szs_layout_part(&end, block * sizeof(uint32_t));
+    layout.pinned_refs = szs_layout_part(&end, refs_total * sizeof(szs_string_ref_t));
     layout.pinned_bytes = end, end = 0;
-    layout.device_counters = layout_part(&end, 3 * sizeof(uint64_t));
-    layout.device_rows = layout_part(&end, block * sizeof(uint32_t));
-    layout.device_refs = layout_part(&end, refs_total * sizeof(szs_string_ref_t));
+    layout.device_counters = szs_layout_part(&end, 3 * sizeof(uint64_t));
+    layout.device_rows = szs_layout_part(&end, block * sizeof(uint32_t));
+    layout.device_refs = szs_layout_part(&end, refs_total * sizeof(szs_string_ref_t));
     layout.device_bytes = end;
     return layout;
 }
@@ -265,19 +189,7 @@ static int row_route(szs_rerank_call_t const *call, size_t query) {
 static size_t rerank_deal_rows(szs_rerank_call_t const *call, size_t q0, size_t rows, uint32_t *order, uint32_t *longest) {
     *longest = 0;
     if (!call->kernel_route) return 0;
-    uint32_t bins[SZS_RERANK_LONGEST_QUERY + 2];
-    size_t kernel_rows = 0;
-    memset(bins, 0, sizeof(bins));
-    for (size_t r = 0; r < rows; ++r)
-        if (row_route(call, q0 + r) == szs_rerank_route_kernel_k) ++bins[SZS_RERANK_LONGEST_QUERY - call->query_lengths[q0 + r] + 1], ++kernel_rows;
-    for (size_t b = 1; b < SZS_RERANK_LONGEST_QUERY + 2; ++b) bins[b] += bins[b - 1];
-    for (size_t r = 0; r < rows; ++r) {
-        if (row_route(call, q0 + r) != szs_rerank_route_kernel_k) continue;
-        uint32_t const length = call->query_lengths[q0 + r];
-        order[bins[SZS_RERANK_LONGEST_QUERY - length]++] = (uint32_t)r;
-        if (length > *longest) *longest = length;
-    }
-    return kernel_rows;
+    return szs_deal_short_rows(call->query_lengths + q0, rows, order, longest);
 }
 
 /**
@@ -409,7 +321,7 @@ static sz_status_t rerank_row(szs_rerank_call_t *call, size_t query, uint64_t co
 
 sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                               size_t const *indices, size_t k, void *scores, size_t row_stride, char const **error_message) {
-    double const started = now_milliseconds();
+    double const started = szs_now_milliseconds();
     if (k < 1 || row_stride < k) return szs_report(sz_unexpected_dimensions_k, error_message, "k must be at least 1 and row_stride at least k");
     if (!engine || engine->magic != SZS_ENGINE_MAGIC || (unsigned)engine->family > szs_family_smith_waterman_k)
         return szs_report(sz_status_unknown_k, error_message, "Engine must be an initialized similarity engine");
@@ -444,12 +356,12 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     if (index_traits.host_readable)
         for (size_t q = 0; q < q_count; ++q)
             for (size_t r = 0; r < k; ++r)
-                if (index_is_bad(call.indices[q * row_stride + r], c_count))
+                if (szs_index_is_bad(call.indices[q * row_stride + r], c_count))
                     return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
 
-    status = host_offsets_of(queries, &engine->host_rerank_offsets[0], stream, &call.query_offsets, error_message);
+    status = szs_host_offsets_of(queries, &engine->host_rerank_offsets[0], stream, &call.query_offsets, error_message);
     if (status == sz_success_k && candidates)
-        status = host_offsets_of(candidates, &engine->host_rerank_offsets[1], stream, &call.pool_offsets, error_message);
+        status = szs_host_offsets_of(candidates, &engine->host_rerank_offsets[1], stream, &call.pool_offsets, error_message);
     if (status != sz_success_k) return status;
     if (!candidates) call.pool_offsets = call.query_offsets;
 
@@ -463,7 +375,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
 
     call.device = device;
     rerank_routes_enabled(engine->family == szs_family_levenshtein_k && engine->is_unit_cost, &call.kernel_route, &call.strips_route);
-    int const refs_needed[2] = {call.kernel_route && side_needs_refs(queries), call.kernel_route && candidates && side_needs_refs(candidates)};
+    int const refs_needed[2] = {call.kernel_route && szs_side_needs_refs(queries), call.kernel_route && candidates && szs_side_needs_refs(candidates)};
     size_t const refs_count[2] = {refs_needed[0] ? q_count : 0, refs_needed[1] ? c_count : 0};
     size_t const gathered = refs_count[0] > refs_count[1] ? refs_count[0] : refs_count[1];
     szs_rerank_layout_t const layout = rerank_layout(q_count, gathered, block, k, index_traits.host_readable, refs_count[0] + refs_count[1]);
@@ -492,7 +404,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
         uint64_t *const addresses = (uint64_t *)(host + layout.host_addresses);
         uint32_t *const lengths = (uint32_t *)(host + layout.host_gathered_lengths);
         int usable = 0;
-        status = kernel_side(queries, call.query_offsets, refs_needed[0], addresses, lengths, pinned_refs, device_refs, stream, &call.sides[0],
+        status = szs_kernel_side(queries, call.query_offsets, refs_needed[0], addresses, lengths, pinned_refs, device_refs, stream, &call.sides[0],
                              &usable, error_message);
         if (status != sz_success_k) return status;
         if (!usable) call.kernel_route = 0;
@@ -500,12 +412,12 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
         for (size_t q = 0; q < q_count && call.kernel_route; ++q) {
             if (refs_needed[0]) call.query_lengths[q] = lengths[q];
             else {
-                uint64_t const from = tape_offset(queries, call.query_offsets, q), to = tape_offset(queries, call.query_offsets, q + 1);
+                uint64_t const from = szs_tape_offset(queries, call.query_offsets, q), to = szs_tape_offset(queries, call.query_offsets, q + 1);
                 call.query_lengths[q] = to >= from && to - from <= SZS_RERANK_LONGEST_STRIPS_QUERY ? (uint32_t)(to - from) : ~0u;
             }
         }
         if (call.kernel_route && candidates) {
-            status = kernel_side(candidates, call.pool_offsets, refs_needed[1], addresses, lengths, pinned_refs + refs_count[0],
+            status = szs_kernel_side(candidates, call.pool_offsets, refs_needed[1], addresses, lengths, pinned_refs + refs_count[0],
                                  device_refs + refs_count[0], stream, &call.sides[1], &usable, error_message);
             if (status != sz_success_k) return status;
             if (!usable) call.kernel_route = 0;
@@ -523,7 +435,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
                 uint64_t length = 0;
                 if (refs_needed[pool_side]) length = lengths[i]; /* the side gathered last: the candidates', or the queries' own */
                 else {
-                    uint64_t const from = tape_offset(call.pool, call.pool_offsets, i), to = tape_offset(call.pool, call.pool_offsets, i + 1);
+                    uint64_t const from = szs_tape_offset(call.pool, call.pool_offsets, i), to = szs_tape_offset(call.pool, call.pool_offsets, i + 1);
                     length = to >= from ? to - from : 0; /* (descending offsets: the kernel reports them) */
                 }
                 if (length > call.longest_candidate) call.longest_candidate = length;
@@ -549,7 +461,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
             if (error == hipSuccess) error = hipStreamSynchronize(stream);
             if (error != hipSuccess) break;
             for (size_t i = 0; i < rows * k && status == sz_success_k; ++i)
-                if (index_is_bad(downloaded[i], c_count))
+                if (szs_index_is_bad(downloaded[i], c_count))
                     status = szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
             if (status != sz_success_k) break;
             host_indices = downloaded, host_indices_stride = k;
@@ -571,7 +483,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     engine->last_profile.pairs = total->pairs, engine->last_profile.algorithmic_bytes = total->algorithmic_bytes;
     engine->last_profile.unique_bytes = total->unique_bytes, engine->last_profile.launches = total->launches;
     engine->last_profile.longest_query = total->longest_query, engine->last_profile.longest_candidate = total->longest_candidate;
-    engine->last_profile.host_milliseconds = now_milliseconds() - started;
+    engine->last_profile.host_milliseconds = szs_now_milliseconds() - started;
     return szs_report(sz_success_k, error_message, NULL);
 }
 

@@ -156,7 +156,7 @@ typedef struct szs_engine_s {
     szs_buffer_t device_top_k_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
     szs_buffer_t device_top_k_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
 
-    /* rerank calls (host/rerank.c) */
+    /* rerank calls (host/rerank.c); fuzzy-find calls (host/fuzzy_find.c) lay their own parts out in the same buffers */
     szs_buffer_t host_rerank_offsets[2]; /* host: tape offsets only the device can read - queries, candidates */
     szs_buffer_t host_rerank;            /* host: query lengths, gathered strings, a block of indices only the device can read, a row's picks */
     szs_buffer_t pinned_rerank;          /* pinned: the kernel's flag, its counters, a row's cells and image, the kernel's rows, refs of both sides */
@@ -390,5 +390,13 @@ sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input
 /** `candidates` NULL: the indices refer to the queries themselves (no index is excluded). */
 sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                               size_t const *indices, size_t k, void *scores, size_t row_stride, char const **error_message);
+
+/* ---- fuzzy find (fuzzy_find.c) ------------------------------------------------------------------------------------------ */
+
+/** `indices` NULL: slot r is candidate r (k = the candidates' count); `candidates` NULL: the indices refer to the queries; `ends` may
+ *  be NULL.  Unit-cost byte Levenshtein engines only.  Uses the engine's rerank buffers. */
+sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                  size_t const *indices, size_t k, size_t *distances, size_t *ends, size_t row_stride,
+                                  char const **error_message);
 
 #endif /* SZS_INTERNAL_H_ */
