@@ -20,6 +20,7 @@
  *    `indices`, a fingerprint search, any outside candidate generator) without a queries x candidates matrix (csrc/host/rerank.c).
  *  - szs_rocm_fuzzy_find*       : the best match of a query INSIDE each listed candidate - fewest edits to some substring, and where it
  *    ends - for a snippet in a document, a primer in a read, a misspelled name in a record (csrc/host/fuzzy_find.c).
+ *  - szs_rocm_fuzzy_find_spans* : the same call with the whole span: where that best match starts as well.
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -169,7 +170,7 @@ SZ_API_RUNTIME sz_status_t szs_rocm_rerank_u64tape(void *engine, szs_device_scop
  *                                      most m, and at most the global distance;
  *      ends[q * row_stride + r]      = the smallest j that attains it   - the exclusive byte offset in c at which the leftmost-ending
  *                                      best match ends; 0: the empty substring (distance m).
- *  Start offsets are not reported.  `ends` may be NULL, `distances` may not.
+ *  Start offsets are szs_rocm_fuzzy_find_spans' (below).  `ends` may be NULL, `distances` may not.
  *
  *  Rows and slots are szs_rocm_rerank's: `indices`, `distances` and `ends` share `row_stride`, in 8-byte cells; slot r of row q pairs
  *  queries[q] with candidates[indices[q * row_stride + r]] for r < k; cells [k, row_stride) are left untouched; k >= 1 and
@@ -204,6 +205,39 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_u64tape(void *engine, szs_device_
                                                        sz_sequence_u64tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
                                                        sz_size_t *distances, sz_size_t *ends, sz_size_t row_stride,
                                                        char const **error_message);
+
+/**
+ *  Fuzzy find with SPANS: szs_rocm_fuzzy_find and, per pair, where the match starts - candidate[start : end] is the snippet to
+ *  highlight, the primer to cut out, the misspelled name to extract.  `distances` and `ends` are exactly szs_rocm_fuzzy_find's, and
+ *
+ *      starts[q * row_stride + r] = end - t*,  t* = the smallest t in [0, min(end, m + distance)] for which the global unit-cost
+ *                                   distance of q and c[end - t : end] equals `distance`
+ *
+ *  - the SHORTEST best match that ends at `end`.  Such a t exists (D[m][end] is the minimum over every start of that distance), none
+ *  gives less, and any t that attains `distance` has |t - m| <= distance: the span is at most m + distance <= 2 m bytes long.
+ *  end = 0 (nothing of the query occurs, or it is empty) gives start = 0; an empty slot gives (0, 0, 0).
+ *
+ *  All three outputs are required: a NULL one is refused with sz_status_unknown_k and nothing is written.  They share `row_stride`
+ *  with `indices`.  Every other rule - rows and slots, the dense and the self form, the two limits, refusals, memory kinds, what a
+ *  failed call leaves behind - is szs_rocm_fuzzy_find's.  A block of rows is TWO launches on the scope's stream: the forward kernel,
+ *  unchanged, and behind it a reverse pass over at most m + distance bytes per pair (csrc/hip/myers_fuzzy_spans.hip).
+ *  szs_rocm_last_call_profile reports launches = 2 per block, pairs as before, and cells = m x n + m x min(end, m + distance) over
+ *  the non-empty slots.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_spans(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                                     sz_sequence_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                     sz_size_t *distances, sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride,
+                                                     char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_spans_u32tape(void *engine, szs_device_scope_t device,
+                                                             sz_sequence_u32tape_t const *queries,
+                                                             sz_sequence_u32tape_t const *candidates, sz_size_t const *indices,
+                                                             sz_size_t k, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                             sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_spans_u64tape(void *engine, szs_device_scope_t device,
+                                                             sz_sequence_u64tape_t const *queries,
+                                                             sz_sequence_u64tape_t const *candidates, sz_size_t const *indices,
+                                                             sz_size_t k, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                             sz_size_t row_stride, char const **error_message);
 
 /**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine

@@ -418,15 +418,19 @@ class _Engine:
         host = results[:rows].cpu().numpy() if stride == k else results[:rows, :k]
         return host.view(self._dtype)
 
-    def fuzzy_find(self, queries, candidates, indices=None, device: Optional[DeviceScope] = None, out=None):
+    def fuzzy_find(self, queries, candidates, indices=None, device: Optional[DeviceScope] = None, out=None, starts=False):
         """The best match of every query INSIDE the candidates listed for it (`szs_rocm_fuzzy_find_*`): returns `(distances, ends)`,
         two `uint64` `(rows, k)` NumPy matrices - `distances[q, r]` is the fewest edits that turn `queries[q]` into some substring of
         `candidates[indices[q, r]]`, `ends[q, r]` the smallest exclusive byte offset at which such a substring ends (0: the empty one).
         `indices` is what `rerank` takes; None is the dense form, every query in every candidate: the results are
         `(rows, len(candidates))`.  `candidates` None: the indices refer to `queries` (and must be given).  2**64 - 1 marks an empty
         slot (0, 0).  `out`: a pair of NumPy arrays or torch tensors of 8-byte cells that share the row stride of `indices`, filled
-        and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes."""
+        and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes.
+        `starts=True` (`szs_rocm_fuzzy_find_spans_*`): returns `(distances, starts, ends)` - `candidates[i][starts[q, r]:ends[q, r]]`
+        is the shortest best match that ends at `ends[q, r]` - and `out` is a triple in that order."""
         import torch
+
+        names = ("out distances", "out starts", "out ends") if starts else ("out distances", "out ends")
 
         queries = _as_strs(queries)
         candidates = None if candidates is None else _as_strs(candidates)
@@ -440,19 +444,19 @@ class _Engine:
             if index_rows != rows:
                 raise ValueError(f"`indices` must have one row per query: {index_rows} rows, {rows} queries")
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise ValueError("`out` must be a pair (distances, ends)")
+            if not isinstance(out, (tuple, list)) or len(out) != len(names):
+                raise ValueError("`out` must be a triple (distances, starts, ends)" if starts else "`out` must be a pair (distances, ends)")
             pointers = []
-            for matrix, name in zip(out, ("out distances", "out ends")):
+            for matrix, name in zip(out, names):
                 pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
                 if stride is not None and own_stride != stride:
                     raise ValueError("`out` and `indices` must share one row stride")
                 stride = own_stride
                 pointers.append(pointer)
-            distances_pointer, ends_pointer = pointers
+            output_pointers = pointers
         scope = device or self._scope or _get_default_scope()
         gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for matrix, name in ((indices, "indices"),) + (tuple(zip(out, ("out distances", "out ends"))) if out is not None else ()):
+        for matrix, name in ((indices, "indices"),) + (tuple(zip(out, names)) if out is not None else ()):
             if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
                 raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
         if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
@@ -461,23 +465,26 @@ class _Engine:
         if out is None:
             if stride is None or stride == k:
                 stride = k
-                results = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
-                distances_pointer, ends_pointer = results[0].data_ptr(), results[1].data_ptr()
+                results = torch.empty((len(names), max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+                output_pointers = [matrix.data_ptr() for matrix in results]
             else:  # the outputs share the stride of the indices: host matrices as wide as theirs
-                results = np.zeros((2, max(rows, 1), stride), dtype=np.int64)
-                distances_pointer, ends_pointer = results[0].ctypes.data, results[1].ctypes.data
+                results = np.zeros((len(names), max(rows, 1), stride), dtype=np.int64)
+                output_pointers = [matrix.ctypes.data for matrix in results]
 
         error = ctypes.c_char_p()
-        call = lib.szs_rocm_fuzzy_find_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_find_u32tape
+        if starts:
+            call = lib.szs_rocm_fuzzy_find_spans_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_find_spans_u32tape
+        else:
+            call = lib.szs_rocm_fuzzy_find_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_find_u32tape
         q_tape = queries._tape(gpu_device)
         c_tape = None if candidates is None else candidates._tape(gpu_device)
         status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
-                      indices_pointer, k, distances_pointer, ends_pointer, stride, ctypes.byref(error))
+                      indices_pointer, k, *output_pointers, stride, ctypes.byref(error))
         _abi.check(status, error)
         if out is not None:
             return out
         host = results[:, :rows].cpu().numpy() if isinstance(results, torch.Tensor) else results[:, :rows, :k]
-        return host[0].view(np.uint64), host[1].view(np.uint64)
+        return tuple(matrix.view(np.uint64) for matrix in host)
 
     def __del__(self):
         handle = getattr(self, "handle", None)

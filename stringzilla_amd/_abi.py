@@ -84,6 +84,7 @@ _FP_CALL = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, 
 _TOP_K = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ERR])
 _RERANK = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ERR])
 _FUZZY_FIND = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ERR])
+_FUZZY_FIND_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 
 SIGNATURES = {
     "szs_version_major": (c_int, []), "szs_version_minor": (c_int, []), "szs_version_patch": (c_int, []),
@@ -137,6 +138,8 @@ SIGNATURES = {
     "szs_rocm_top_k": _TOP_K, "szs_rocm_top_k_u32tape": _TOP_K, "szs_rocm_top_k_u64tape": _TOP_K,
     "szs_rocm_rerank": _RERANK, "szs_rocm_rerank_u32tape": _RERANK, "szs_rocm_rerank_u64tape": _RERANK,
     "szs_rocm_fuzzy_find": _FUZZY_FIND, "szs_rocm_fuzzy_find_u32tape": _FUZZY_FIND, "szs_rocm_fuzzy_find_u64tape": _FUZZY_FIND,
+    "szs_rocm_fuzzy_find_spans": _FUZZY_FIND_SPANS, "szs_rocm_fuzzy_find_spans_u32tape": _FUZZY_FIND_SPANS,
+    "szs_rocm_fuzzy_find_spans_u64tape": _FUZZY_FIND_SPANS,
     "szs_rocm_rerank_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "szs_rocm_fingerprint_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t,
                                              c_void_p, c_size_t, ERR]),

@@ -79,4 +79,38 @@ struct text_stream_t {
     }
 };
 
+/**
+ *  The backward twin of text_stream_t: the bytes of one string per lane from its LAST byte down, four at a time.
+ *
+ *  Group `back` = 0, 1, ... holds bytes [length - 4 back - 4, length - 4 back) of the string, the last of them in its top byte:
+ *  `splice(raw(back), raw(back + 1))`.  The same rule holds: only aligned dwords that contain a byte of the string are loaded -
+ *  a dword above the last byte or below the first reads as zero, and its bytes are never consumed by a caller that counts its
+ *  columns against `length`.
+ */
+struct text_stream_backward_t {
+    u32 const *aligned_base; // string address rounded down to 4 bytes
+    u32 byte_shift;          // (string address + length) & 3: where the first group begins in its low dword
+    u32 valid_dwords;        // dwords [0, valid_dwords) contain string bytes
+    u32 top_dword;           // the dword in which the byte BEHIND the last one lies
+
+    __device__ __forceinline__ text_stream_backward_t(u64 address, u32 length) {
+        aligned_base = reinterpret_cast<u32 const *>(address & ~(u64)3);
+        u64 const top = (address & 3) + (u64)length; // below 2^32 + 3: a string has less than 4 GiB
+        byte_shift = (u32)(top & 3);
+        valid_dwords = length ? (u32)((top + 3) / 4) : 0;
+        top_dword = (u32)(top / 4);
+    }
+
+    /** Dword `back` below the top one; zero outside the string (an index below dword 0 wraps to one beyond `valid_dwords`). */
+    __device__ __forceinline__ u32 raw(u32 back) const {
+        u32 const dword_index = top_dword - back;
+        return dword_index < valid_dwords ? aligned_base[dword_index] : 0u;
+    }
+
+    /** Text bytes [length - 4 back - 4, length - 4 back) given raw dwords `back` and `back + 1`. */
+    __device__ __forceinline__ u32 splice(u32 raw_high, u32 raw_low) const {
+        return __builtin_amdgcn_alignbyte(raw_high, raw_low, byte_shift);
+    }
+};
+
 } // namespace szs_hip

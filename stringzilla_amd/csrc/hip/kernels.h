@@ -331,6 +331,20 @@ int szs_hip_levenshtein_fuzzy_find(szs_rerank_side_t const *queries, szs_rerank_
                                    uint64_t k, uint64_t *distances, uint64_t *ends, uint64_t outputs_stride, unsigned widest,
                                    uint32_t *flags, unsigned long long *counters, void *stream);
 
+/**
+ *  Where those matches start (hip/myers_fuzzy_spans.hip): launched on the same stream BEHIND szs_hip_levenshtein_fuzzy_find with the
+ *  same sides, rows, indices, `k`, `outputs_stride` and `widest`, it reads the `distances` and `ends` that launch wrote and stores
+ *  starts[row * outputs_stride + r] = end - t*, t* the smallest t in [0, min(end, m + distance)] for which the global distance of
+ *  the query and candidate[end - t : end] is `distance` - the shortest best match that ends at `end`.  An empty slot receives 0.
+ *  A `distance` above the query's length or an `end` above the candidate's is never used to address anything and sets
+ *  `flags[SZS_RERANK_FLAG_TAPE]`.  `counters`: [1] += m x the window's bytes, [2] += m + the window's bytes; [0] is left alone.
+ */
+int szs_hip_levenshtein_fuzzy_starts(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,
+                                     uint32_t const *rows, uint32_t rows_count, uint64_t const *indices, uint64_t indices_stride,
+                                     uint64_t k, uint64_t const *distances, uint64_t const *ends, uint64_t *starts,
+                                     uint64_t outputs_stride, unsigned widest, uint32_t *flags, unsigned long long *counters,
+                                     void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {

@@ -155,6 +155,31 @@ __device__ __forceinline__ u32 myers_infix_column(u32 (&vp)[words_], u32 (&vn)[w
     return (hp_below >> 31) | ((hn_below >> 31) << 1);
 }
 
+/** One column of the GLOBAL matrix whose bottom-row score is followed (D[0][j] = j: every prefix of the text against the whole
+ *  pattern): myers_column's `+1` entering bit 0, and the horizontal pair of the vector's LAST row coming back as hp | hn << 1, as in
+ *  myers_infix_column - myers_strip_column(vp, vn, eq, 1, 0) with myers_column's materialisation (hip/myers_fuzzy_spans.hip). */
+template <int words_>
+__device__ __forceinline__ u32 myers_prefix_column(u32 (&vp)[words_], u32 (&vn)[words_], u32 const (&eq)[words_]) {
+    u32 carry = 0, hp_below = 0, hn_below = 0;
+#pragma unroll
+    for (int w = 0; w < words_; ++w) {
+        u32 const xv = eq[w] | vn[w];
+        u32 carry_out;
+        u32 const sum = __builtin_addc(eq[w] & vp[w], vp[w], carry, &carry_out);
+        carry = carry_out;
+        u32 const d0 = (sum ^ vp[w]) | eq[w];
+        u32 const hp = vn[w] | ~(d0 | vp[w]);
+        u32 const hn = vp[w] & d0;
+        u32 const hp_shifted = w == 0 ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
+        u32 const hn_shifted = w == 0 ? (hn << 1) : __builtin_amdgcn_alignbit(hn, hn_below, 31);
+        hp_below = hp, hn_below = hn;
+        vp[w] = hn_shifted | ~(xv | hp_shifted);
+        vn[w] = hp_shifted & xv;
+        if constexpr (words_ > 1) asm("" : "+v"(vp[w]), "+v"(vn[w])); // as in myers_column: both new vectors materialised
+    }
+    return (hp_below >> 31) | ((hn_below >> 31) << 1);
+}
+
 /** One column of one strip; `hp_in` / `hn_in` are the deltas entering the strip's first row as 0 / 1 values; the bit pair
  *  leaving its last row comes back as hp | hn << 1. */
 template <int words_>

@@ -1,7 +1,9 @@
 /*
  *  fuzzy_find.c - the best match of a query INSIDE each listed candidate (szs_rocm_fuzzy_find*, include/stringzillas/stringzillas_rocm.h;
  *  DESIGN.md section 4.9): distances[q][r] = the fewest edits that turn queries[q] into some substring of candidates[indices[q][r]],
- *  ends[q][r] = the smallest exclusive byte offset at which such a substring ends.
+ *  ends[q][r] = the smallest exclusive byte offset at which such a substring ends; szs_rocm_fuzzy_find_spans* add starts[q][r] = where
+ *  the shortest such substring that ends there begins - a second launch (hip/myers_fuzzy_spans.hip) behind the first, on the same
+ *  stream and inside the same event pair, and only in a call that asks for it.
  *
  *  The shape is rerank.c's kernel route alone (rerank_internal.h has what the two share): blocks of at most 2^20 rows, every row of a
  *  block in ONE launch of hip/myers_fuzzy_find.hip, dealt by descending query length; the kernel reads the indices and writes the
@@ -58,8 +60,8 @@ typedef struct {
     hipStream_t stream;
     size_t k, row_stride, block;
     uint64_t const *indices; /* NULL: the dense form */
-    uint64_t *distances, *ends;
-    int stage_indices, stage_distances, stage_ends;
+    uint64_t *distances, *ends, *starts; /* `starts` NULL: the plain call - one launch a block */
+    int stage_indices, stage_distances, stage_ends, stage_starts;
     szs_rerank_side_t sides[2];
     uint32_t *query_lengths, *flags, *order, *device_order;
     uint64_t *landed;
@@ -67,7 +69,8 @@ typedef struct {
     szs_rocm_call_profile_t total;
 } szs_fuzzy_find_call_t;
 
-/** One block: stages what the device cannot reach, launches the kernel once over every row, brings the outputs home, reads the flags. */
+/** One block: stages what the device cannot reach, launches the kernel once over every row - and the kernel of the starts behind it,
+ *  where the call asks for them - brings the outputs home, reads the flags. */
 static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size_t rows, hipError_t *hip_error, char const **error_message) {
     szs_engine_s *const engine = call->engine;
     hipStream_t const stream = call->stream;
@@ -79,17 +82,19 @@ static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size
     uint64_t *staged = (uint64_t *)engine->device_rerank_staged.pointer;
     uint64_t const *kernel_indices = call->indices ? call->indices + q0 * row_stride : NULL;
     uint64_t *kernel_distances = call->distances + q0 * row_stride, *kernel_ends = call->ends ? call->ends + q0 * row_stride : NULL;
+    uint64_t *kernel_starts = call->starts ? call->starts + q0 * row_stride : NULL;
     size_t indices_stride = row_stride;
     hipError_t error = hipSuccess;
     if (call->stage_indices) {
         error = hipMemcpy2DAsync(staged, row_bytes, call->indices + q0 * row_stride, pitch, row_bytes, rows, hipMemcpyHostToDevice, stream);
         kernel_indices = staged, indices_stride = k, staged += call->block * k;
     }
-    /* the kernel's two outputs share one stride: both staged (dense), or both the caller's */
-    int const dense_outputs = call->stage_distances || call->stage_ends;
+    /* the kernels' outputs share one stride: all staged (dense), or all the caller's */
+    int const dense_outputs = call->stage_distances || call->stage_ends || call->stage_starts;
     if (dense_outputs) {
         kernel_distances = staged, staged += call->block * k;
-        if (call->ends) kernel_ends = staged;
+        if (call->ends) kernel_ends = staged, staged += call->block * k;
+        if (call->starts) kernel_starts = staged;
     }
     size_t const outputs_stride = dense_outputs ? k : row_stride;
     memset(call->flags, 0, SZS_RERANK_FLAGS * sizeof(uint32_t));
@@ -100,6 +105,10 @@ static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size
         error = (hipError_t)szs_hip_levenshtein_fuzzy_find(&call->sides[0], &call->sides[1], q0, call->device_order, (uint32_t)dealt,
                                                            kernel_indices, indices_stride, k, kernel_distances, kernel_ends, outputs_stride,
                                                            widest, call->flags, call->device_counters, stream);
+    if (error == hipSuccess && call->starts) /* behind the first launch on the same stream: it reads what that one wrote */
+        error = (hipError_t)szs_hip_levenshtein_fuzzy_starts(&call->sides[0], &call->sides[1], q0, call->device_order, (uint32_t)dealt,
+                                                             kernel_indices, indices_stride, k, kernel_distances, kernel_ends, kernel_starts,
+                                                             outputs_stride, widest, call->flags, call->device_counters, stream);
     if (error == hipSuccess) error = hipEventRecord(engine->event_stop, stream);
     if (error == hipSuccess) error = hipMemcpyAsync(call->landed, call->device_counters, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
     if (error == hipSuccess && dense_outputs)
@@ -108,6 +117,9 @@ static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size
     if (error == hipSuccess && dense_outputs && call->ends)
         error = hipMemcpy2DAsync(call->ends + q0 * row_stride, pitch, kernel_ends, row_bytes, row_bytes, rows,
                                  call->stage_ends ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream);
+    if (error == hipSuccess && dense_outputs && call->starts)
+        error = hipMemcpy2DAsync(call->starts + q0 * row_stride, pitch, kernel_starts, row_bytes, row_bytes, rows,
+                                 call->stage_starts ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream);
     hipError_t const drained = hipStreamSynchronize(stream);
     if (error == hipSuccess) error = drained;
     if (error != hipSuccess) {
@@ -121,23 +133,25 @@ static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size
     float milliseconds = 0;
     if (hipEventElapsedTime(&milliseconds, engine->event_start, engine->event_stop) != hipSuccess) (void)hipGetLastError();
     szs_rocm_call_profile_t *const total = &call->total;
-    total->kernel_milliseconds += milliseconds, total->launches += 1;
-    total->pairs += call->landed[0], total->cells += call->landed[1];
-    total->algorithmic_bytes += call->landed[2] + call->landed[0] * (2 * 4 + 8 + (call->ends ? 8 : 0));
+    total->kernel_milliseconds += milliseconds, total->launches += call->starts ? 2 : 1;
+    total->pairs += call->landed[0], total->cells += call->landed[1]; /* with starts: the cells and bytes of the reverse windows too */
+    total->algorithmic_bytes += call->landed[2] + call->landed[0] * (2 * 4 + 8 + (call->ends ? 8 : 0) + (call->starts ? 8 : 0));
     if (longest > total->longest_query) total->longest_query = longest;
     return sz_success_k;
 }
 
-sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
-                                  size_t const *indices, size_t k, size_t *distances, size_t *ends, size_t row_stride,
-                                  char const **error_message) {
+/** The one call path.  `starts` set: the starts are computed too.  `missing`: the message for a required output that is NULL, refused
+ *  behind the checks of the dimensions, the engine and an empty batch; NULL when the entry has all it requires. */
+static sz_status_t fuzzy_find_call(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                   size_t const *indices, size_t k, size_t *distances, size_t *starts, size_t *ends, size_t row_stride,
+                                   char const *missing, char const **error_message) {
     double const started = szs_now_milliseconds();
     if (k < 1 || row_stride < k) return szs_report(sz_unexpected_dimensions_k, error_message, "k must be at least 1 and row_stride at least k");
     if (!engine || engine->magic != SZS_ENGINE_MAGIC || engine->family != szs_family_levenshtein_k || !engine->is_unit_cost)
         return szs_report(sz_status_unknown_k, error_message, "Fuzzy find needs an initialized unit-cost byte Levenshtein engine");
     if (!queries) return szs_report(sz_status_unknown_k, error_message, "Queries must not be null");
     if (!queries->count) return szs_report(sz_success_k, error_message, NULL);
-    if (!distances) return szs_report(sz_status_unknown_k, error_message, "Distances must not be null");
+    if (missing) return szs_report(sz_status_unknown_k, error_message, missing);
     szs_input_t const *const pool = candidates ? candidates : queries; /* the self form: the indices refer to the queries */
     size_t const q_count = queries->count, c_count = pool->count;
     if (!indices && k != c_count)
@@ -160,6 +174,7 @@ sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_
     memset(&call, 0, sizeof(call));
     call.engine = engine, call.stream = stream, call.k = k, call.row_stride = row_stride;
     call.indices = (uint64_t const *)indices, call.distances = (uint64_t *)distances, call.ends = (uint64_t *)ends;
+    call.starts = (uint64_t *)starts;
 
     /* indices the host can read: validated before anything is launched */
     if (indices && szs_classify_pointer(indices).host_readable)
@@ -178,8 +193,9 @@ sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_
     call.stage_indices = indices && !szs_classify_pointer(indices).device_accessible;
     call.stage_distances = !szs_classify_pointer(distances).device_accessible;
     call.stage_ends = ends && !szs_classify_pointer(ends).device_accessible;
-    int const dense_outputs = call.stage_distances || call.stage_ends;
-    size_t const staged_arrays = (size_t)call.stage_indices + (dense_outputs ? 1 + (ends != NULL) : 0);
+    call.stage_starts = starts && !szs_classify_pointer(starts).device_accessible;
+    int const dense_outputs = call.stage_distances || call.stage_ends || call.stage_starts;
+    size_t const staged_arrays = (size_t)call.stage_indices + (dense_outputs ? 1 + (ends != NULL) + (starts != NULL) : 0);
     size_t block = q_count < SZS_RERANK_MOST_ROWS ? q_count : SZS_RERANK_MOST_ROWS;
     if (staged_arrays && block > SZS_RERANK_STAGE_BYTES / (k * sizeof(uint64_t))) block = SZS_RERANK_STAGE_BYTES / (k * sizeof(uint64_t));
     if (block < 1) block = 1;
@@ -244,4 +260,18 @@ sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_
     engine->last_profile = call.total; /* the sums over the call; every other field blank */
     engine->last_profile.host_milliseconds = szs_now_milliseconds() - started;
     return szs_report(sz_success_k, error_message, NULL);
+}
+
+sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                  size_t const *indices, size_t k, size_t *distances, size_t *ends, size_t row_stride,
+                                  char const **error_message) {
+    return fuzzy_find_call(engine, scope, queries, candidates, indices, k, distances, NULL, ends, row_stride,
+                           distances ? NULL : "Distances must not be null", error_message);
+}
+
+sz_status_t szs_engine_fuzzy_find_spans(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                        size_t const *indices, size_t k, size_t *distances, size_t *starts, size_t *ends,
+                                        size_t row_stride, char const **error_message) {
+    char const *const missing = !distances ? "Distances must not be null" : !starts || !ends ? "Starts and ends must not be null" : NULL;
+    return fuzzy_find_call(engine, scope, queries, candidates, indices, k, distances, starts, ends, row_stride, missing, error_message);
 }

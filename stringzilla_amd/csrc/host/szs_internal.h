@@ -398,5 +398,9 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
 sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                                   size_t const *indices, size_t k, size_t *distances, size_t *ends, size_t row_stride,
                                   char const **error_message);
+/** The same call with `starts`: where the shortest best match that ends at `ends` begins.  All three outputs are required. */
+sz_status_t szs_engine_fuzzy_find_spans(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                        size_t const *indices, size_t k, size_t *distances, size_t *starts, size_t *ends,
+                                        size_t row_stride, char const **error_message);
 
 #endif /* SZS_INTERNAL_H_ */
