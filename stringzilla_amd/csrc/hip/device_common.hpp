@@ -77,6 +77,9 @@ struct text_stream_t {
     __device__ __forceinline__ u32 splice(u32 raw_low, u32 raw_high) const {
         return __builtin_amdgcn_alignbyte(raw_high, raw_low, byte_shift);
     }
+
+    /** Byte `step` = 0 ... 3 of a spliced dword, in the order the stream walks: the lowest byte first. */
+    __device__ __forceinline__ static u32 symbol(u32 symbols, int step) { return (symbols >> (8 * step)) & 0xFFu; }
 };
 
 /**
@@ -111,6 +114,9 @@ struct text_stream_backward_t {
     __device__ __forceinline__ u32 splice(u32 raw_high, u32 raw_low) const {
         return __builtin_amdgcn_alignbyte(raw_high, raw_low, byte_shift);
     }
+
+    /** Byte `step` = 0 ... 3 of a spliced group, in the order the stream walks: the top byte first. */
+    __device__ __forceinline__ static u32 symbol(u32 symbols, int step) { return (symbols >> (8 * (3 - step))) & 0xFFu; }
 };
 
 } // namespace szs_hip

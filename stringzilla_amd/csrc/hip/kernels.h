@@ -276,7 +276,9 @@ int szs_hip_fingerprint_matches_u64(uint32_t const *queries, uint64_t queries_st
  *  dynamic LDS); a longer one is not scored and sets `flags[SZS_RERANK_FLAG_UNFIT]`.  An index of ~0 is an empty
  *  slot: score 0, no string touched.  Any other index >= the candidates' count is never used to address anything and sets
  *  `flags[SZS_RERANK_FLAG_INDEX]`; offsets that descend or a string of 4 GiB and more set `flags[SZS_RERANK_FLAG_TAPE]`.  `flags`:
- *  SZS_RERANK_FLAGS words of pinned host memory, zeroed by the caller, one per kind of failure - every store is the same 1.  `counters` (three qwords of device memory, zeroed by the caller): [0] += scored pairs, [1] += their cells, [2] += their bytes.
+ *  SZS_RERANK_FLAGS words of pinned host memory, zeroed by the caller, one per kind of failure - every store is the same 1.
+ *  `counters` (three qwords of device memory, zeroed by the caller): [0] += scored pairs, [1] += their cells, [2] += their bytes.
+ *  Rows, groups, sides, indices, flags and counters are what every kernel over listed pairs below shares: hip/rerank_core.hpp.
  */
 typedef struct szs_rerank_side_t {
     void const *offsets;          /* tapes: count + 1 entries */
@@ -297,8 +299,8 @@ int szs_hip_levenshtein_rerank(szs_rerank_side_t const *queries, szs_rerank_side
                                void *stream);
 
 /**
- *  Rerank rows whose query is longer than that (hip/myers_rerank_strips.hip): the same rows, groups, indices, flags and counters,
- *  the query walked as STRIPS of 1 ... 8 words - as few as 8 words allow, all of one width (a 300-byte query: two strips of 5
+ *  Rerank rows whose query is longer than that (hip/myers_rerank_strips.hip): rows, groups, indices, flags and counters as above
+ *  (hip/rerank_core.hpp), the query walked as STRIPS of 1 ... 8 words - as few as 8 words allow, all of one width (a 300-byte query: two strips of 5
  *  words) - with the horizontal deltas under a strip's last row parked in `parked`, 16 text columns to a dword.  `rows` should
  *  arrive by DESCENDING word count of the query: the rows of a wavefront run at the strip count and width of its longest query.
  *  Every query of `rows` has at most SZS_RERANK_LONGEST_STRIPS_QUERY bytes (shorter ones, 256 bytes and less included, are scored
@@ -323,7 +325,7 @@ int szs_hip_levenshtein_rerank_strips(szs_rerank_side_t const *queries, szs_rera
  *  Fuzzy find (hip/myers_fuzzy_find.hip; host/fuzzy_find.c): the best match of a query INSIDE each listed
  *  candidate - distances[row * outputs_stride + r] = the fewest edits that turn the query into some substring of the candidate, and
  *  (`ends` not NULL) ends[...] = the smallest exclusive byte offset in the candidate at which such a substring ends.  Rows, groups,
- *  sides, `widest`, flags and counters are szs_hip_levenshtein_rerank's; `indices` NULL: slot r is candidate r.  An empty slot
+ *  sides, `widest`, flags and counters are hip/rerank_core.hpp's, as szs_hip_levenshtein_rerank describes them; `indices` NULL: slot r is candidate r.  An empty slot
  *  receives distance 0 and end 0.
  */
 int szs_hip_levenshtein_fuzzy_find(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,

@@ -1,13 +1,8 @@
 /*
  *  myers_rerank_strips.hip - unit-cost byte Levenshtein distances of LISTED pairs whose query is a DOCUMENT: more than 256 and at
  *  most 65,536 bytes (szs_rocm_rerank*, host/rerank.c).  The twin of hip/myers_rerank.hip for the rows its
- *  256-row bit-vector cannot hold; everything about rows, groups, indices, flags and counters is that kernel's:
- *
- *  - A GROUP of L = 16 / 32 / 64 lanes serves one row, one listed candidate per lane fetched THROUGH the index (`index < count`
- *    before every use), rows of more than 64 candidates in chunks of 64; a workgroup is ONE wavefront of 64 / L rows, so there is
- *    no workgroup barrier; empty slots score 0 and touch no string; scores leave as ordinary 8-byte vector stores.
- *
- *  New here:
+ *  256-row bit-vector cannot hold; groups, rows, indices, flags and counters are hip/rerank_core.hpp's.  Empty slots score 0 and
+ *  touch no string; scores leave as ordinary 8-byte vector stores.  This kernel's own:
  *
  *  - STRIPS.  The query is cut into strips of equal width W = 1 ... 8 words, as few as 8 words allow (SZS_RERANK_STRIPS_OF,
  *    SZS_RERANK_STRIP_WORDS_OF: a 300-byte query is two strips of 5 words, not 8 + 2) - the sizing rule of
@@ -36,36 +31,30 @@ namespace szs_hip {
 constexpr u32 rerank_strip_table_dwords_k = peq_layout<SZS_RERANK_STRIP_WORDS>::total_dwords; // 8 KB: a table of any W fits
 
 /**
- *  The rows of one wavefront as `strips` strips of `words_` words.  `has_row`, `row`, `query_address`, `query_length` are uniform
- *  within a group of `lanes_` lanes; `strips` is uniform within the wavefront.  `parked_mine`: this lane's column of the
- *  workgroup's parked array, `parked_dwords` dwords of 16 text columns each, 64 dwords apart.
+ *  The rows of one wavefront as `strips` strips of `words_` words; `strips` is uniform within the wavefront.  `parked_mine`: this
+ *  lane's column of the workgroup's parked array, `parked_dwords` dwords of 16 text columns each, 64 dwords apart.
  */
 template <int words_, int lanes_>
-__device__ __forceinline__ void rerank_strip_rows(u32 *table, u32 strips, bool has_row, u64 row, u64 query_address, u32 query_length,
-                                                  szs_rerank_side_t const &candidates, u64 const *__restrict__ indices, u64 indices_stride,
-                                                  u64 k, u64 *__restrict__ scores, u64 scores_stride, u32 *parked_mine, u32 parked_dwords,
-                                                  u32 *flags, unsigned long long *counters) {
+__device__ __forceinline__ void rerank_strip_rows(u32 *table, u32 strips, listed_row_t const &row, szs_rerank_side_t const &candidates,
+                                                  u64 const *__restrict__ indices, u64 indices_stride, u64 k, u64 *__restrict__ scores,
+                                                  u64 scores_stride, u32 *parked_mine, u32 parked_dwords, u32 *flags,
+                                                  unsigned long long *counters) {
     using layout = peq_layout<words_, byte_rows_k>;
     constexpr u32 strip_rows = 32u * words_;
     u32 const sub = threadIdx.x % lanes_;
-    u32 const pad = strips * strip_rows - query_length; // phantom low rows of THIS row (a row without a query: all of them)
-    u8 const *const pattern = reinterpret_cast<u8 const *>(query_address);
+    u32 const pad = strips * strip_rows - row.query_length; // phantom low rows of THIS row (a row without a query: all of them)
+    u8 const *const pattern = reinterpret_cast<u8 const *>(row.query_address);
 
-    u64 pairs = 0, cells = 0, bytes = 0;
+    listed_counters_t counted;
 #pragma unroll 1
     for (u64 first = 0; first < k; first += lanes_) { // uniform: every row of the call has k slots
-        u64 const rank = first + sub;
-        bool live = has_row && rank < k;
+        u64 const rank = first + sub, at = row.row * scores_stride + rank;
         u64 address = 0;
         u32 text_length = 0;
-        if (live) {
-            u64 const index = indices[row * indices_stride + rank];
-            if (index == ~0ull) scores[row * scores_stride + rank] = 0, live = false; // an empty slot: no string is touched
-            else if (index >= candidates.count) flags[SZS_RERANK_FLAG_INDEX] = 1u, live = false; // never used to address anything
-            else if (!rerank_fetch(candidates, index, address, text_length)) flags[SZS_RERANK_FLAG_TAPE] = 1u, live = false, text_length = 0;
-            else if (((u64)text_length + 15u) / 16u > parked_dwords) // the host's job to prevent: nothing is parked for it
-                flags[SZS_RERANK_FLAG_UNFIT] = 1u, live = false, text_length = 0;
-        }
+        bool live = row.has_row && rank < k &&
+                    listed_candidate(candidates, indices[row.row * indices_stride + rank], [&]() { scores[at] = 0; }, flags, address, text_length);
+        if (live && ((u64)text_length + 15u) / 16u > parked_dwords) // the host's job to prevent: nothing is parked for it
+            flags[SZS_RERANK_FLAG_UNFIT] = 1u, live = false, text_length = 0;
         u32 const longest_in_wave = wave_max_u32(text_length);
         u32 const shortest_in_wave = ~wave_max_u32(live ? ~text_length : 0u); // over live lanes; none: ~0, and the longest is 0
         text_stream_t const text(address, text_length);
@@ -147,15 +136,11 @@ __device__ __forceinline__ void rerank_strip_rows(u32 *table, u32 strips, bool h
         }
 
         if (live) {
-            scores[row * scores_stride + rank] = (u64)((i64)text_length + delta_sum);
-            pairs += 1, cells += (u64)query_length * text_length, bytes += (u64)query_length + text_length;
+            scores[at] = (u64)((i64)text_length + delta_sum);
+            counted.add(row.query_length, text_length);
         }
     }
-    pairs = wave_sum_u64(pairs), cells = wave_sum_u64(cells), bytes = wave_sum_u64(bytes);
-    if (threadIdx.x == 0 && pairs) {
-        atomicAdd(&counters[0], (unsigned long long)pairs), atomicAdd(&counters[1], (unsigned long long)cells);
-        atomicAdd(&counters[2], (unsigned long long)bytes);
-    }
+    counted.land(counters, true);
 }
 
 template <int lanes_>
@@ -173,37 +158,14 @@ __global__ __launch_bounds__(64) void levenshtein_rerank_strips_kernel(szs_reran
 
 #pragma unroll 1
     for (u64 first_slot = (u64)blockIdx.x * groups; first_slot < rows_count; first_slot += (u64)gridDim.x * groups) { // uniform
-        u64 const slot = first_slot + group;
-        bool has_row = slot < rows_count;
-        u64 const row = has_row ? rows[slot] : 0;
-        u64 query_address = 0;
-        u32 query_length = 0;
-        if (has_row) {
-            u64 const query = first_query + row;
-            if (query >= queries.count || !rerank_fetch(queries, query, query_address, query_length)) flags[SZS_RERANK_FLAG_TAPE] = 1u, has_row = false;
-            else if (query_length > SZS_RERANK_LONGEST_STRIPS_QUERY) flags[SZS_RERANK_FLAG_UNFIT] = 1u, has_row = false; // the host's job to prevent
-            if (!has_row) query_length = 0;
-        }
+        listed_row_t const row = listed_row(queries, first_query, rows, rows_count, first_slot + group, SZS_RERANK_LONGEST_STRIPS_QUERY, flags);
         // every row at the strip count and width of the wavefront's longest query - scalars, so one of the eight bodies runs
-        u32 const longest = (u32)__builtin_amdgcn_readfirstlane((int)wave_max_u32(query_length));
-        u32 const words = SZS_RERANK_WORDS_OF(longest);
+        u32 const words = SZS_RERANK_WORDS_OF(listed_longest_query(row));
         u32 const strips = SZS_RERANK_STRIPS_OF(words);
-#define SZS_RERANK_STRIPS_BODY(W)                                                                                                          \
-    case W:                                                                                                                                 \
-        rerank_strip_rows<W, lanes_>(table, strips, has_row, row, query_address, query_length, candidates, indices, indices_stride, k,      \
-                                     scores, scores_stride, parked_mine, parked_dwords, flags, counters);                                   \
-        break;
-        switch (SZS_RERANK_STRIP_WORDS_OF(words)) {
-            SZS_RERANK_STRIPS_BODY(1)
-            SZS_RERANK_STRIPS_BODY(2)
-            SZS_RERANK_STRIPS_BODY(3)
-            SZS_RERANK_STRIPS_BODY(4)
-            SZS_RERANK_STRIPS_BODY(5)
-            SZS_RERANK_STRIPS_BODY(6)
-            SZS_RERANK_STRIPS_BODY(7)
-        default: SZS_RERANK_STRIPS_BODY(8)
-        }
-#undef SZS_RERANK_STRIPS_BODY
+        listed_at_width(SZS_RERANK_STRIP_WORDS_OF(words), [&](auto width) {
+            rerank_strip_rows<decltype(width)::value, lanes_>(table, strips, row, candidates, indices, indices_stride, k, scores, scores_stride,
+                                                              parked_mine, parked_dwords, flags, counters);
+        });
     }
 }
 
@@ -216,14 +178,9 @@ extern "C" int szs_hip_levenshtein_rerank_strips(szs_rerank_side_t const *querie
     using namespace szs_hip;
     if (!rows_count || !k) return 0;
     if (!workgroups || !parked || !parked_dwords || !queries || !candidates || !flags || !counters) return (int)hipErrorInvalidValue;
-    unsigned const lanes = szs_hip_rerank_lanes(k);
-    hipStream_t const s = static_cast<hipStream_t>(stream);
-#define SZS_RERANK_STRIPS_LAUNCH(L)                                                                                                    \
-    hipLaunchKernelGGL(levenshtein_rerank_strips_kernel<L>, dim3(workgroups), dim3(wave_size_k), 0, s, *queries, *candidates, first_query, \
-                       rows, rows_count, indices, indices_stride, k, scores, scores_stride, parked, parked_dwords, flags, counters)
-    if (lanes == 16) SZS_RERANK_STRIPS_LAUNCH(16);
-    else if (lanes == 32) SZS_RERANK_STRIPS_LAUNCH(32);
-    else SZS_RERANK_STRIPS_LAUNCH(64);
-#undef SZS_RERANK_STRIPS_LAUNCH
-    return (int)hipGetLastError();
+    return listed_launch(k, [&](auto lanes) {
+        hipLaunchKernelGGL(levenshtein_rerank_strips_kernel<decltype(lanes)::value>, dim3(workgroups), dim3(wave_size_k), 0,
+                           static_cast<hipStream_t>(stream), *queries, *candidates, first_query, rows, rows_count, indices, indices_stride, k,
+                           scores, scores_stride, parked, parked_dwords, flags, counters);
+    });
 }

@@ -17,7 +17,8 @@
  *  Indices the host can read are validated before anything is launched; indices only the device can read are checked by the kernel
  *  (`index < count` before every use, a flag in pinned memory) - or, for the rows of the row route, downloaded and validated first.
  *
- *  szs_engine_rerank checks the arguments, lays out the scratch (rerank_layout), prepares the sides and walks the blocks; per block:
+ *  szs_engine_rerank checks the arguments and walks the blocks on the skeleton of listed_pairs.c (rerank_internal.h: the preamble, the
+ *  scratch, the sides, the bracket around a block's launches); per block:
  *  rerank_deal_rows and rerank_deal_strip_rows (which rows each kernel takes, longest query first), rerank_kernel_rows (staging, at
  *  most one launch of each kernel, the scores home), rerank_row (the row route).  The routes write disjoint rows of `scores`, so none
  *  depends on running before another.  szs_rocm_rerank_probe reports the routing of bare lengths through the same functions.
@@ -68,77 +69,20 @@ static void add_profile(szs_rocm_call_profile_t *total, szs_rocm_call_profile_t 
     if (part->longest_candidate > total->longest_candidate) total->longest_candidate = part->longest_candidate;
 }
 
-/* ---- scratch layouts ------------------------------------------------------------------------------------------------------ */
-
-/** Byte offsets of every part of the engine's rerank buffers: computed in ONE place, each part behind the one before it. */
-typedef struct {
-    /* engine->host_rerank */
-    size_t host_query_lengths;    /* u32 x queries */
-    size_t host_addresses;        /* u64 x gathered strings of the larger side */
-    size_t host_gathered_lengths; /* u32 x the same */
-    size_t host_indices;          /* u64 x block x k: a block of indices only the device can read (else empty) */
-    size_t host_picks;            /* u64 x k: a row's non-empty indices */
-    size_t host_bytes;
-    /* engine->pinned_rerank */
-    size_t pinned_flags;   /* u32 x SZS_RERANK_FLAGS: the kernel's */
-    size_t pinned_landed;  /* u64 x 3: the kernel's counters, downloaded */
-    size_t pinned_cells;   /* u64 x k: a row's scores as the engine call leaves them */
-    size_t pinned_image;   /* u64 x k: the row as it is written */
-    size_t pinned_rows;    /* u32 x block: the kernel's rows */
-    size_t pinned_refs;    /* refs of the queries, then of the candidates */
-    size_t pinned_bytes;
-    /* engine->device_rerank */
-    size_t device_counters; /* u64 x 3 */
-    size_t device_rows;     /* u32 x block */
-    size_t device_refs;     /* as pinned_refs */
-    size_t device_bytes;
-} szs_rerank_layout_t;
-
-static szs_rerank_layout_t rerank_layout(size_t q_count, size_t gathered, size_t block, size_t k, int indices_on_host, size_t refs_total) {
-    szs_rerank_layout_t layout;
-    size_t end = 0;
-    layout.host_query_lengths = szs_layout_part(&end, q_count * sizeof(uint32_t));
-    layout.host_addresses = szs_layout_part(&end, gathered * sizeof(uint64_t));
-    layout.host_gathered_lengths = szs_layout_part(&end, gathered * sizeof(uint32_t));
-    layout.host_indices = szs_layout_part(&end, indices_on_host ? 0 : block * k * sizeof(uint64_t));
-    layout.host_picks = szs_layout_part(&end, k * sizeof(uint64_t));
-    layout.host_bytes = end, end = 0;
-    layout.pinned_flags = szs_layout_part(&end, SZS_RERANK_FLAGS * sizeof(uint32_t));
-    layout.pinned_landed = szs_layout_part(&end, 3 * sizeof(uint64_t));
-    layout.pinned_cells = szs_layout_part(&end, k * sizeof(uint64_t));
-    layout.pinned_image = szs_layout_part(&end, k * sizeof(uint64_t));
-    layout.pinned_rows = szs_layout_part(&end, block * sizeof(uint32_t));
-    layout.pinned_refs = szs_layout_part(&end, refs_total * sizeof(szs_string_ref_t));
-    layout.pinned_bytes = end, end = 0;
-    layout.device_counters = szs_layout_part(&end, 3 * sizeof(uint64_t));
-    layout.device_rows = szs_layout_part(&end, block * sizeof(uint32_t));
-    layout.device_refs = szs_layout_part(&end, refs_total * sizeof(szs_string_ref_t));
-    layout.device_bytes = end;
-    return layout;
-}
-
 /* ---- the call ------------------------------------------------------------------------------------------------------------ */
 
 /** What the parts of one call share. */
 typedef struct {
-    szs_engine_s *engine;
+    szs_listed_call_t listed; /* query_lengths: filled with kernel_route, ~0 where no kernel takes the row */
     szs_scope_s *scope;
-    hipStream_t stream;
     szs_input_t const *queries, *pool; /* pool: the candidates, or the queries in the self form */
-    void const *query_offsets, *pool_offsets;
-    size_t k, row_stride, block;
     uint64_t const *indices;
     uint64_t *scores;
     int scores_on_host, stage_indices, stage_scores;
-    int device;
     int kernel_route, strips_route; /* may rows take hip/myers_rerank.hip, and hip/myers_rerank_strips.hip */
     uint64_t longest_candidate;     /* strips_route: over the whole candidate side */
-    szs_rerank_side_t sides[2];
-    uint32_t *query_lengths; /* kernel_route: per query, ~0 where no kernel takes it */
-    uint64_t *picks, *landed, *row_cells, *row_image;
-    uint32_t *flags, *order, *device_order;
-    unsigned long long *device_counters;
-    szs_rocm_call_profile_t total;
+    uint64_t *picks, *row_cells, *row_image; /* the row route's: a row's non-empty indices, its scores as the engine call leaves
+                                                them, the row as it is written */
     int engine_calls;
 } szs_rerank_call_t;
 
@@ -182,14 +126,14 @@ static szs_rerank_strips_grid_t rerank_strips_grid(size_t rows, size_t k, uint64
 }
 
 static int row_route(szs_rerank_call_t const *call, size_t query) {
-    return call->kernel_route ? rerank_route_of(call->kernel_route, call->strips_route, call->query_lengths[query]) : szs_rerank_route_row_k;
+    return call->kernel_route ? rerank_route_of(call->kernel_route, call->strips_route, call->listed.query_lengths[query]) : szs_rerank_route_row_k;
 }
 
 /** The short kernel's rows of block [q0, q0 + rows) into `order`, longest query first (a counting sort of the lengths 256 ... 0). */
 static size_t rerank_deal_rows(szs_rerank_call_t const *call, size_t q0, size_t rows, uint32_t *order, uint32_t *longest) {
     *longest = 0;
     if (!call->kernel_route) return 0;
-    return szs_deal_short_rows(call->query_lengths + q0, rows, order, longest);
+    return szs_deal_short_rows(call->listed.query_lengths + q0, rows, order, longest);
 }
 
 /**
@@ -205,11 +149,11 @@ static size_t rerank_deal_strip_rows(szs_rerank_call_t const *call, size_t q0, s
     memset(bins, 0, sizeof(bins));
     for (size_t r = 0; r < rows; ++r)
         if (row_route(call, q0 + r) == szs_rerank_route_strips_k)
-            ++bins[most_words - SZS_RERANK_WORDS_OF(call->query_lengths[q0 + r]) + 1], ++strip_rows;
+            ++bins[most_words - SZS_RERANK_WORDS_OF(call->listed.query_lengths[q0 + r]) + 1], ++strip_rows;
     for (size_t b = 1; b < most_words + 2; ++b) bins[b] += bins[b - 1];
     for (size_t r = 0; r < rows; ++r) {
         if (row_route(call, q0 + r) != szs_rerank_route_strips_k) continue;
-        uint32_t const length = call->query_lengths[q0 + r];
+        uint32_t const length = call->listed.query_lengths[q0 + r];
         order[bins[most_words - SZS_RERANK_WORDS_OF(length)]++] = (uint32_t)r;
         if (length > *longest) *longest = length;
     }
@@ -224,12 +168,13 @@ static size_t rerank_deal_strip_rows(szs_rerank_call_t const *call, size_t q0, s
  */
 static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t rows, size_t short_rows, uint32_t longest_short,
                                       size_t strip_rows, uint32_t longest_strips, hipError_t *hip_error, char const **error_message) {
-    szs_engine_s *const engine = call->engine;
-    hipStream_t const stream = call->stream;
-    size_t const k = call->k, row_stride = call->row_stride, row_bytes = k * sizeof(uint64_t);
+    szs_listed_call_t *const listed = &call->listed;
+    szs_engine_s *const engine = listed->engine;
+    hipStream_t const stream = listed->stream;
+    size_t const k = listed->k, row_stride = listed->row_stride, row_bytes = k * sizeof(uint64_t);
     szs_rerank_strips_grid_t const grid = rerank_strips_grid(strip_rows, k, call->longest_candidate);
     if (strip_rows) {
-        sz_status_t const status = szs_buffer_reserve(&engine->device_rerank_parked, szs_memory_device_k, call->device, grid.bytes, error_message);
+        sz_status_t const status = szs_buffer_reserve(&engine->device_rerank_parked, szs_memory_device_k, listed->device, grid.bytes, error_message);
         if (status != sz_success_k) return status;
     }
     uint64_t *const staged = (uint64_t *)engine->device_rerank_staged.pointer;
@@ -244,24 +189,19 @@ static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t
                                  hipMemcpyHostToDevice, stream);
         kernel_indices = staged, kernel_indices_stride = k;
     }
-    if (call->stage_scores) kernel_scores = staged + (call->stage_indices ? call->block * k : 0), kernel_scores_stride = k;
-    memset(call->flags, 0, SZS_RERANK_FLAGS * sizeof(uint32_t));
-    if (error == hipSuccess) error = hipMemsetAsync(call->device_counters, 0, 3 * sizeof(uint64_t), stream);
-    if (error == hipSuccess)
-        error = hipMemcpyAsync(call->device_order, call->order, (short_rows + strip_rows) * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-    if (error == hipSuccess) error = hipEventRecord(engine->event_start, stream);
+    if (call->stage_scores) kernel_scores = staged + (call->stage_indices ? listed->block * k : 0), kernel_scores_stride = k;
+    error = szs_listed_block_begin(listed, short_rows + strip_rows, error);
     if (error == hipSuccess && short_rows)
-        error = (hipError_t)szs_hip_levenshtein_rerank(&call->sides[0], &call->sides[1], q0, call->device_order, (uint32_t)short_rows,
+        error = (hipError_t)szs_hip_levenshtein_rerank(&listed->sides[0], &listed->sides[1], q0, listed->device_order, (uint32_t)short_rows,
                                                        kernel_indices, kernel_indices_stride, k, kernel_scores, kernel_scores_stride, widest,
-                                                       call->flags, call->device_counters, stream);
+                                                       listed->flags, listed->device_counters, stream);
     if (error == hipSuccess && strip_rows)
-        error = (hipError_t)szs_hip_levenshtein_rerank_strips(&call->sides[0], &call->sides[1], q0, call->device_order + short_rows,
+        error = (hipError_t)szs_hip_levenshtein_rerank_strips(&listed->sides[0], &listed->sides[1], q0, listed->device_order + short_rows,
                                                               (uint32_t)strip_rows, kernel_indices, kernel_indices_stride, k, kernel_scores,
                                                               kernel_scores_stride, grid.workgroups,
                                                               (uint32_t *)engine->device_rerank_parked.pointer, grid.parked_dwords,
-                                                              call->flags, call->device_counters, stream);
-    if (error == hipSuccess) error = hipEventRecord(engine->event_stop, stream);
-    if (error == hipSuccess) error = hipMemcpyAsync(call->landed, call->device_counters, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+                                                              listed->flags, listed->device_counters, stream);
+    error = szs_listed_block_end(listed, error);
     for (size_t r = 0; r < rows && error == hipSuccess && call->stage_scores;) {
         if (row_route(call, q0 + r) == szs_rerank_route_row_k) {
             ++r;
@@ -273,47 +213,33 @@ static sz_status_t rerank_kernel_rows(szs_rerank_call_t *call, size_t q0, size_t
                                  run - r, hipMemcpyDeviceToHost, stream);
         r = run;
     }
-    hipError_t const drained = hipStreamSynchronize(stream);
-    if (error == hipSuccess) error = drained;
-    if (error != hipSuccess) {
-        *hip_error = error;
-        return sz_success_k;
-    }
-    if (call->flags[SZS_RERANK_FLAG_UNFIT]) return szs_report(sz_status_unknown_k, error_message, "A query or a candidate beyond what the rerank kernels were sized for");
-    if (call->flags[SZS_RERANK_FLAG_TAPE]) return szs_report(sz_unexpected_dimensions_k, error_message, "Tape offsets must ascend");
-    if (call->flags[SZS_RERANK_FLAG_INDEX]) return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
-    float milliseconds = 0;
-    if (hipEventElapsedTime(&milliseconds, engine->event_start, engine->event_stop) != hipSuccess) (void)hipGetLastError();
-    szs_rocm_call_profile_t *const total = &call->total;
-    total->kernel_milliseconds += milliseconds, total->launches += (short_rows != 0) + (strip_rows != 0);
-    total->pairs += call->landed[0], total->cells += call->landed[1];
-    total->algorithmic_bytes += call->landed[2] + call->landed[0] * (2 * 4 + 8);
-    if (longest > total->longest_query) total->longest_query = longest;
-    return sz_success_k;
+    return szs_listed_block_finish(listed, error, hip_error, (short_rows != 0) + (strip_rows != 0), longest, 2 * 4 + 8, sz_status_unknown_k,
+                                   "A query or a candidate beyond what the rerank kernels were sized for", error_message);
 }
 
 /** The row route of one row: one engine call of 1 x k' over the row's non-empty indices, scattered into the row. */
 static sz_status_t rerank_row(szs_rerank_call_t *call, size_t query, uint64_t const *row_indices, hipError_t *hip_error,
                               char const **error_message) {
-    size_t const k = call->k;
+    szs_engine_s *const engine = call->listed.engine;
+    size_t const k = call->listed.k;
     size_t listed = 0;
     for (size_t i = 0; i < k; ++i)
         if (row_indices[i] != SZS_RERANK_EMPTY) call->picks[listed++] = row_indices[i];
     if (listed) {
         uint64_t const query_pick = query;
         szs_gathered_sequence_t query_wrapper, candidate_wrapper;
-        szs_input_t const one = gather_input(call->queries, call->query_offsets, &query_pick, 1, &query_wrapper);
-        szs_input_t const few = gather_input(call->pool, call->pool_offsets, call->picks, listed, &candidate_wrapper);
-        sz_status_t const status = szs_engine_cross(call->engine, call->scope, &one, &few, call->row_cells, listed, error_message); /* synchronous */
+        szs_input_t const one = gather_input(call->queries, call->listed.offsets[0], &query_pick, 1, &query_wrapper);
+        szs_input_t const few = gather_input(call->pool, call->listed.offsets[1], call->picks, listed, &candidate_wrapper);
+        sz_status_t const status = szs_engine_cross(engine, call->scope, &one, &few, call->row_cells, listed, error_message); /* synchronous */
         if (status != sz_success_k) return status;
-        add_profile(&call->total, &call->engine->last_profile), ++call->engine_calls;
+        add_profile(&call->listed.total, &engine->last_profile), ++call->engine_calls;
     }
     for (size_t i = 0, next = 0; i < k; ++i) call->row_image[i] = row_indices[i] != SZS_RERANK_EMPTY ? call->row_cells[next++] : 0;
-    uint64_t *const row_scores = call->scores + query * call->row_stride;
+    uint64_t *const row_scores = call->scores + query * call->listed.row_stride;
     if (call->scores_on_host) memcpy(row_scores, call->row_image, k * sizeof(uint64_t));
     else { /* (the image is free again once this copy has run: nothing writes it before the next synchronisation) */
-        hipError_t error = hipMemcpyAsync(row_scores, call->row_image, k * sizeof(uint64_t), hipMemcpyHostToDevice, call->stream);
-        if (error == hipSuccess) error = hipStreamSynchronize(call->stream);
+        hipError_t error = hipMemcpyAsync(row_scores, call->row_image, k * sizeof(uint64_t), hipMemcpyHostToDevice, call->listed.stream);
+        if (error == hipSuccess) error = hipStreamSynchronize(call->listed.stream);
         *hip_error = error;
     }
     return sz_success_k;
@@ -331,99 +257,54 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     if (!scores) return szs_report(sz_status_unknown_k, error_message, "Scores must not be null");
     if (k > (~(size_t)0 >> 4) / sizeof(uint64_t)) return szs_report(sz_overflow_risk_k, error_message, NULL);
 
-    int device = 0;
-    hipStream_t stream = NULL;
-    sz_status_t status = szs_scope_bind_gpu(scope, &device, &stream, error_message);
-    if (status != sz_success_k) return status;
-    szs_engine_follow_device(engine, device);
-    if (engine->events_device != device) {
-        hipError_t error = hipEventCreate(&engine->event_start);
-        if (error == hipSuccess) error = hipEventCreate(&engine->event_stop);
-        if (error != hipSuccess) return szs_report_hip(error, error_message);
-        engine->events_device = device;
-    }
-
     szs_rerank_call_t call;
     memset(&call, 0, sizeof(call));
-    call.engine = engine, call.scope = scope, call.stream = stream, call.queries = queries;
+    szs_listed_call_t *const listed = &call.listed;
+    sz_status_t status = szs_listed_open(listed, engine, scope, k, row_stride, error_message);
+    if (status != sz_success_k) return status;
+    hipStream_t const stream = listed->stream;
+    call.scope = scope, call.queries = queries;
     call.pool = candidates ? candidates : queries; /* the self form: the indices refer to the queries */
-    call.k = k, call.row_stride = row_stride, call.indices = (uint64_t const *)indices, call.scores = (uint64_t *)scores;
+    call.indices = (uint64_t const *)indices, call.scores = (uint64_t *)scores;
     size_t const q_count = queries->count, c_count = call.pool->count;
     szs_pointer_traits_t const index_traits = szs_classify_pointer(indices), score_traits = szs_classify_pointer(scores);
     call.scores_on_host = score_traits.host_readable;
 
     /* indices the host can read: validated before anything is launched */
-    if (index_traits.host_readable)
-        for (size_t q = 0; q < q_count; ++q)
-            for (size_t r = 0; r < k; ++r)
-                if (szs_index_is_bad(call.indices[q * row_stride + r], c_count))
-                    return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
-
-    status = szs_host_offsets_of(queries, &engine->host_rerank_offsets[0], stream, &call.query_offsets, error_message);
-    if (status == sz_success_k && candidates)
-        status = szs_host_offsets_of(candidates, &engine->host_rerank_offsets[1], stream, &call.pool_offsets, error_message);
+    if (index_traits.host_readable && !szs_listed_indices_ok(call.indices, q_count, k, row_stride, c_count))
+        return szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
+    status = szs_listed_offsets(listed, queries, candidates, error_message);
     if (status != sz_success_k) return status;
-    if (!candidates) call.pool_offsets = call.query_offsets;
 
-    /* blocks of rows: the kernel's row list and - where the device cannot reach the caller's arrays - their dense copies in budget */
+    /* blocks of rows: the kernel's row list and - where the device cannot reach the caller's arrays, or the host the indices that
+       the row route needs - their dense copies in budget */
     call.stage_indices = !index_traits.device_accessible, call.stage_scores = !score_traits.device_accessible;
-    size_t block = q_count < SZS_RERANK_MOST_ROWS ? q_count : SZS_RERANK_MOST_ROWS;
-    if ((call.stage_indices || call.stage_scores || !index_traits.host_readable) && block > SZS_RERANK_STAGE_BYTES / (k * sizeof(uint64_t)))
-        block = SZS_RERANK_STAGE_BYTES / (k * sizeof(uint64_t));
-    if (block < 1) block = 1;
-    call.block = block;
+    size_t const block = listed->block =
+        szs_listed_block_rows(q_count, k, call.stage_indices || call.stage_scores || !index_traits.host_readable);
 
-    call.device = device;
     rerank_routes_enabled(engine->family == szs_family_levenshtein_k && engine->is_unit_cost, &call.kernel_route, &call.strips_route);
-    int const refs_needed[2] = {call.kernel_route && szs_side_needs_refs(queries), call.kernel_route && candidates && szs_side_needs_refs(candidates)};
-    size_t const refs_count[2] = {refs_needed[0] ? q_count : 0, refs_needed[1] ? c_count : 0};
-    size_t const gathered = refs_count[0] > refs_count[1] ? refs_count[0] : refs_count[1];
-    szs_rerank_layout_t const layout = rerank_layout(q_count, gathered, block, k, index_traits.host_readable, refs_count[0] + refs_count[1]);
-
-    status = szs_buffer_reserve(&engine->host_rerank, szs_memory_host_k, 0, layout.host_bytes, error_message);
-    if (status == sz_success_k) status = szs_buffer_reserve(&engine->pinned_rerank, szs_memory_pinned_k, device, layout.pinned_bytes, error_message);
-    if (status == sz_success_k && call.kernel_route)
-        status = szs_buffer_reserve(&engine->device_rerank, szs_memory_device_k, device, layout.device_bytes, error_message);
-    if (status == sz_success_k && call.kernel_route && (call.stage_indices || call.stage_scores))
-        status = szs_buffer_reserve(&engine->device_rerank_staged, szs_memory_device_k, device,
-                                    ((size_t)call.stage_indices + (size_t)call.stage_scores) * block * k * sizeof(uint64_t), error_message);
+    /* the row route's parts of the scratch: a block of indices only the device can read (else empty) and a row's picks on the host,
+       a row's cells and its image in pinned memory */
+    size_t const host_extra[2] = {index_traits.host_readable ? 0 : block * k * sizeof(uint64_t), k * sizeof(uint64_t)};
+    size_t const pinned_extra[2] = {k * sizeof(uint64_t), k * sizeof(uint64_t)};
+    void *extras[4];
+    status = szs_listed_reserve(listed, queries, candidates, call.kernel_route, host_extra, pinned_extra,
+                                (size_t)call.stage_indices + (size_t)call.stage_scores, extras, error_message);
     if (status != sz_success_k) return status;
-    char *const host = (char *)engine->host_rerank.pointer, *const pinned = (char *)engine->pinned_rerank.pointer;
-    char *const remote = (char *)engine->device_rerank.pointer;
-    uint64_t *const downloaded = (uint64_t *)(host + layout.host_indices);
-    call.query_lengths = (uint32_t *)(host + layout.host_query_lengths), call.picks = (uint64_t *)(host + layout.host_picks);
-    call.flags = (uint32_t *)(pinned + layout.pinned_flags), call.landed = (uint64_t *)(pinned + layout.pinned_landed);
-    call.row_cells = (uint64_t *)(pinned + layout.pinned_cells), call.row_image = (uint64_t *)(pinned + layout.pinned_image);
-    call.order = (uint32_t *)(pinned + layout.pinned_rows);
+    uint64_t *const downloaded = (uint64_t *)extras[0];
+    call.picks = (uint64_t *)extras[1], call.row_cells = (uint64_t *)extras[2], call.row_image = (uint64_t *)extras[3];
 
     if (call.kernel_route) {
-        call.device_counters = (unsigned long long *)(remote + layout.device_counters);
-        call.device_order = (uint32_t *)(remote + layout.device_rows);
-        szs_string_ref_t *const pinned_refs = (szs_string_ref_t *)(pinned + layout.pinned_refs);
-        szs_string_ref_t *const device_refs = (szs_string_ref_t *)(remote + layout.device_refs);
-        uint64_t *const addresses = (uint64_t *)(host + layout.host_addresses);
-        uint32_t *const lengths = (uint32_t *)(host + layout.host_gathered_lengths);
+        /* a side the kernels cannot read: every row takes the row route */
         int usable = 0;
-        status = szs_kernel_side(queries, call.query_offsets, refs_needed[0], addresses, lengths, pinned_refs, device_refs, stream, &call.sides[0],
-                             &usable, error_message);
+        status = szs_listed_prepare_queries(listed, queries, SZS_RERANK_LONGEST_STRIPS_QUERY, &usable, error_message);
         if (status != sz_success_k) return status;
         if (!usable) call.kernel_route = 0;
-        /* the lengths of the queries: which rows the kernel takes, and the order it takes them in */
-        for (size_t q = 0; q < q_count && call.kernel_route; ++q) {
-            if (refs_needed[0]) call.query_lengths[q] = lengths[q];
-            else {
-                uint64_t const from = szs_tape_offset(queries, call.query_offsets, q), to = szs_tape_offset(queries, call.query_offsets, q + 1);
-                call.query_lengths[q] = to >= from && to - from <= SZS_RERANK_LONGEST_STRIPS_QUERY ? (uint32_t)(to - from) : ~0u;
-            }
-        }
-        if (call.kernel_route && candidates) {
-            status = szs_kernel_side(candidates, call.pool_offsets, refs_needed[1], addresses, lengths, pinned_refs + refs_count[0],
-                                 device_refs + refs_count[0], stream, &call.sides[1], &usable, error_message);
+        if (call.kernel_route) {
+            status = szs_listed_prepare_candidates(listed, candidates, &usable, error_message);
             if (status != sz_success_k) return status;
             if (!usable) call.kernel_route = 0;
         }
-        else if (call.kernel_route)
-            call.sides[1] = call.sides[0];
         /* the strips route: sized by the longest string of the candidate side - looked for only when a row would take it */
         int wanted = 0;
         for (size_t q = 0; q < q_count && call.kernel_route && call.strips_route && !wanted; ++q)
@@ -433,9 +314,9 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
             int const pool_side = candidates ? 1 : 0;
             for (size_t i = 0; i < c_count; ++i) {
                 uint64_t length = 0;
-                if (refs_needed[pool_side]) length = lengths[i]; /* the side gathered last: the candidates', or the queries' own */
+                if (listed->refs_needed[pool_side]) length = listed->gathered_lengths[i]; /* the side gathered last: the candidates', or the queries' own */
                 else {
-                    uint64_t const from = szs_tape_offset(call.pool, call.pool_offsets, i), to = szs_tape_offset(call.pool, call.pool_offsets, i + 1);
+                    uint64_t const from = szs_tape_offset(call.pool, listed->offsets[1], i), to = szs_tape_offset(call.pool, listed->offsets[1], i + 1);
                     length = to >= from ? to - from : 0; /* (descending offsets: the kernel reports them) */
                 }
                 if (length > call.longest_candidate) call.longest_candidate = length;
@@ -448,8 +329,8 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block) {
         size_t const rows = q_count - q0 < block ? q_count - q0 : block;
         uint32_t longest_short = 0, longest_strips = 0;
-        size_t const short_rows = rerank_deal_rows(&call, q0, rows, call.order, &longest_short);
-        size_t const strip_rows = rerank_deal_strip_rows(&call, q0, rows, call.order + short_rows, &longest_strips);
+        size_t const short_rows = rerank_deal_rows(&call, q0, rows, listed->order, &longest_short);
+        size_t const strip_rows = rerank_deal_strip_rows(&call, q0, rows, listed->order + short_rows, &longest_strips);
         size_t const kernel_rows = short_rows + strip_rows;
 
         /* the rows of the row route need their indices on the host: downloaded and validated before anything is launched */
@@ -460,9 +341,8 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
                                      k * sizeof(uint64_t), rows, hipMemcpyDeviceToHost, stream);
             if (error == hipSuccess) error = hipStreamSynchronize(stream);
             if (error != hipSuccess) break;
-            for (size_t i = 0; i < rows * k && status == sz_success_k; ++i)
-                if (szs_index_is_bad(downloaded[i], c_count))
-                    status = szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
+            if (!szs_listed_indices_ok(downloaded, rows, k, k, c_count))
+                status = szs_report(sz_unexpected_dimensions_k, error_message, "An index is beyond the candidates");
             if (status != sz_success_k) break;
             host_indices = downloaded, host_indices_stride = k;
         }
@@ -478,7 +358,7 @@ sz_status_t szs_engine_rerank(szs_engine_s *engine, szs_scope_s *scope, szs_inpu
     if (error != hipSuccess) return szs_report_hip(error, error_message);
     /* the profile of a rerank call: the last engine call's (none: blank), with the sums over the launch and every engine call */
     if (!call.engine_calls) memset(&engine->last_profile, 0, sizeof(engine->last_profile));
-    szs_rocm_call_profile_t const *const total = &call.total;
+    szs_rocm_call_profile_t const *const total = &listed->total;
     engine->last_profile.kernel_milliseconds = total->kernel_milliseconds, engine->last_profile.cells = total->cells;
     engine->last_profile.pairs = total->pairs, engine->last_profile.algorithmic_bytes = total->algorithmic_bytes;
     engine->last_profile.unique_bytes = total->unique_bytes, engine->last_profile.launches = total->launches;

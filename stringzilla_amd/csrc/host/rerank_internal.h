@@ -1,7 +1,8 @@
 /*
  *  rerank_internal.h - what the calls over LISTED pairs share on the host (rerank.c: szs_rocm_rerank*; fuzzy_find.c:
- *  szs_rocm_fuzzy_find*): the block and staging budgets, tape offsets where the host can read them, a side as the kernels read it
- *  (szs_rerank_side_t), the parts of a scratch layout, the deal of a block's rows by descending query length.
+ *  szs_rocm_fuzzy_find*): the block and staging budgets, the deal of a block's rows by descending query length, and the skeleton of
+ *  such a call (listed_pairs.c): its preamble, the validation of indices, the scratch, the two sides as the kernels read them, and
+ *  the bracket around a block's launches.  Policy stays with the callers: which engines, which lengths, what an unusable side means.
  */
 #ifndef SZS_RERANK_INTERNAL_H_
 #define SZS_RERANK_INTERNAL_H_
@@ -25,67 +26,73 @@ static inline uint64_t szs_tape_offset(szs_input_t const *input, void const *off
     return input->kind == szs_input_u32tape_k ? ((uint32_t const *)offsets)[i] : ((uint64_t const *)offsets)[i];
 }
 
-/** The offsets of a tape where the host can read them: as they are, or copied to the host - once per call. */
-static inline sz_status_t szs_host_offsets_of(szs_input_t const *input, szs_buffer_t *copy, hipStream_t stream, void const **offsets,
-                                              char const **error_message) {
-    *offsets = input->offsets;
-    if (input->kind == szs_input_sequence_k) return sz_success_k;
-    if (!input->offsets) return szs_report(sz_status_unknown_k, error_message, "Tape offsets must not be null");
-    if (szs_classify_pointer(input->offsets).host_readable) return sz_success_k;
-    size_t const bytes = (input->count + 1) * (input->kind == szs_input_u32tape_k ? 4 : 8);
-    sz_status_t const status = szs_buffer_reserve(copy, szs_memory_host_k, 0, bytes, error_message);
-    if (status != sz_success_k) return status;
-    hipError_t error = hipMemcpyAsync(copy->pointer, input->offsets, bytes, hipMemcpyDeviceToHost, stream);
-    if (error == hipSuccess) error = hipStreamSynchronize(stream);
-    if (error != hipSuccess) return szs_report_hip(error, error_message);
-    *offsets = copy->pointer;
-    return sz_success_k;
-}
+/** What the blocks of one call over listed pairs share. */
+typedef struct {
+    szs_engine_s *engine;
+    hipStream_t stream;
+    int device;
+    size_t k, row_stride, block;
+    void const *offsets[2];  /* of the queries' tape and of the pool's, where the host can read them */
+    szs_rerank_side_t sides[2];
+    uint32_t *query_lengths; /* per query; ~0: more than the call takes, or offsets that descend */
+    uint32_t *flags, *order, *device_order;
+    uint64_t *landed;
+    unsigned long long *device_counters;
+    szs_rocm_call_profile_t total;
+    /* the scratch of the two sides, between szs_listed_reserve and szs_listed_prepare_* */
+    int refs_needed[2];
+    size_t refs_count[2];
+    uint64_t *addresses;
+    uint32_t *gathered_lengths; /* of the side prepared last, where it needed refs */
+    szs_string_ref_t *pinned_refs, *device_refs;
+} szs_listed_call_t;
 
-static inline size_t szs_align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+/** The preamble: binds the scope's GPU, makes the engine follow the device, creates the engine's event pair once per device. */
+sz_status_t szs_listed_open(szs_listed_call_t *call, szs_engine_s *engine, szs_scope_s *scope, size_t k, size_t row_stride,
+                            char const **error_message);
 
-/** One part of a scratch layout: `bytes` at `*end`, each part behind the one before it. */
-static inline size_t szs_layout_part(size_t *end, size_t bytes) {
-    size_t const at = *end;
-    *end = at + szs_align16(bytes);
-    return at;
-}
+/** Is every index of `rows` rows of `k` slots, `row_stride` apart, empty or below `count`?  For indices the host can read: validated
+ *  before anything is launched. */
+int szs_listed_indices_ok(uint64_t const *indices, size_t rows, size_t k, size_t row_stride, size_t count);
 
-/** A side does not need refs when it is a tape whose offsets the device reads itself. */
-static inline int szs_side_needs_refs(szs_input_t const *input) {
-    return input->kind == szs_input_sequence_k || !szs_classify_pointer(input->offsets).device_accessible;
-}
+/** The offsets of both tapes where the host can read them: as they are, or copied to the host - once per call.  `candidates` NULL:
+ *  the self form, the pool is the queries. */
+sz_status_t szs_listed_offsets(szs_listed_call_t *call, szs_input_t const *queries, szs_input_t const *candidates,
+                               char const **error_message);
+
+/** The rows of a block: what the kernel's row list takes and - `within_stage_budget` - what keeps a dense copy of k slots a row
+ *  within SZS_RERANK_STAGE_BYTES. */
+size_t szs_listed_block_rows(size_t q_count, size_t k, int within_stage_budget);
 
 /**
- *  One side as the kernel reads it: the tape itself, or refs in index order built on the host and uploaded.  `*usable` 0: the kernel
- *  cannot reach the side's strings (or its offsets are malformed).
+ *  The scratch of a call, laid out in ONE place and reserved in the engine's rerank buffers (szs_internal.h: grow-only, released
+ *  with the engine): query lengths, gathered addresses and lengths on the host; flags, landed counters, row list and refs in pinned
+ *  memory; counters, row list and refs on the device.  The caller's extra parts - `host_extra` and `pinned_extra` bytes, two each -
+ *  come back as `extras[0 .. 4)`.  `kernels` 0: no kernel will run - no refs, no device buffers.  `staged_arrays`: dense copies of a
+ *  block x k array for what the device cannot reach.  `call->block` is set by the caller.
  */
-static inline sz_status_t szs_kernel_side(szs_input_t const *input, void const *offsets, int needs_refs, uint64_t *addresses,
-                                          uint32_t *lengths, szs_string_ref_t *pinned_refs, szs_string_ref_t *device_refs,
-                                          hipStream_t stream, szs_rerank_side_t *side, int *usable, char const **error_message) {
-    memset(side, 0, sizeof(*side));
-    side->count = input->count, *usable = 1;
-    if (!needs_refs) {
-        side->offsets = input->offsets, side->base = (uint64_t)(uintptr_t)input->data, side->wide = input->kind == szs_input_u64tape_k;
-        uint64_t const bytes = szs_tape_offset(input, offsets, input->count) - szs_tape_offset(input, offsets, 0);
-        *usable = !bytes || szs_classify_pointer(input->data).device_accessible;
-        return sz_success_k;
-    }
-    char const *ignored = NULL;
-    uint64_t bytes = 0;
-    if (szs_gather_strings(input, offsets, addresses, lengths, &bytes, NULL, &ignored) != sz_success_k) {
-        *usable = 0;
-        return sz_success_k;
-    }
-    for (size_t i = 0; i < input->count; ++i)
-        pinned_refs[i].address = addresses[i], pinned_refs[i].length = lengths[i], pinned_refs[i].index = (uint32_t)i;
-    side->refs = device_refs;
-    if (!input->count) return sz_success_k;
-    hipError_t const error = hipMemcpyAsync(device_refs, pinned_refs, input->count * sizeof(szs_string_ref_t), hipMemcpyHostToDevice, stream);
-    return error == hipSuccess ? sz_success_k : szs_report_hip(error, error_message);
-}
+sz_status_t szs_listed_reserve(szs_listed_call_t *call, szs_input_t const *queries, szs_input_t const *candidates, int kernels,
+                               size_t const host_extra[2], size_t const pinned_extra[2], size_t staged_arrays, void *extras[4],
+                               char const **error_message);
 
-static inline int szs_index_is_bad(uint64_t index, size_t count) { return index != SZS_RERANK_EMPTY && index >= count; }
+/** The queries as the kernels read them, and their lengths: ~0 for one of more than `longest_query` bytes or one whose offsets
+ *  descend.  `*usable` 0: the kernels cannot reach the strings (or the side is malformed) - the lengths are not filled in. */
+sz_status_t szs_listed_prepare_queries(szs_listed_call_t *call, szs_input_t const *queries, uint32_t longest_query, int *usable,
+                                       char const **error_message);
+/** The candidates as the kernels read them; NULL: the self form, the queries' side again. */
+sz_status_t szs_listed_prepare_candidates(szs_listed_call_t *call, szs_input_t const *candidates, int *usable, char const **error_message);
+
+/**
+ *  The bracket around a block's launches, each step only while `error` is hipSuccess.  `begin`: clears the flags and the device's
+ *  counters, uploads `dealt` rows of `order`, records the start.  `end`: records the stop, downloads the counters.  `finish`: drains
+ *  the stream - a HIP error goes to `*hip_error` - maps the kernels' flags to a status (UNFIT: the caller's `unfit_status` and
+ *  `unfit_message`), reads the elapsed time and adds the block to `call->total`: `launches`, the counters, `bytes_per_pair` of
+ *  offsets, indices and outputs for every scored pair.  Staging copies between them stay with the caller.
+ */
+hipError_t szs_listed_block_begin(szs_listed_call_t *call, size_t dealt, hipError_t error);
+hipError_t szs_listed_block_end(szs_listed_call_t *call, hipError_t error);
+sz_status_t szs_listed_block_finish(szs_listed_call_t *call, hipError_t error, hipError_t *hip_error, unsigned launches, uint32_t longest,
+                                    size_t bytes_per_pair, sz_status_t unfit_status, char const *unfit_message, char const **error_message);
 
 /**
  *  The rows of a block whose query has at most SZS_RERANK_LONGEST_QUERY bytes into `order`, longest query first (a counting sort of

@@ -119,6 +119,38 @@ def test_empty_slots_padding_and_duplicates(gpu, oracle, rerank_knob, knob):
     assert (wide_scores[4, :k] == 0).all()
 
 
+def test_descending_offsets_of_a_candidate_are_refused_by_every_kernel(gpu, oracle):
+    """A listed candidate whose offsets descend: each of the four kernels refuses it before it addresses anything (the TAPE flag), the
+    call reports it, and with the offset restored the same calls answer as the oracle and the plain DP do."""
+    from test_gpu_fuzzy_spans import dense, listed, same
+
+    rng = random.Random(17)
+    short, long = _rand(rng, 4, 5, 40, b"ACGT"), _rand(rng, 4, 300, 400, b"ACGT")
+    queries = [short[0], long[0], short[1], long[1], short[2], long[2], short[3], long[3]]  # one call, both rerank kernels
+    plain = _rand(rng, 12, 10, 60, b"ACGT")
+    candidates = szs.Strs(plain).to_device(0)
+    indices = np.random.default_rng(17).integers(0, len(plain), size=(len(queries), 4), dtype=np.uint64)
+    indices[:, 1] = 5  # every row lists candidate 5
+    engine = szs.LevenshteinDistances(capabilities=gpu)
+    calls = [lambda: engine.rerank(queries, candidates, indices, device=gpu),
+             lambda: engine.fuzzy_find(short, candidates, indices[:4], device=gpu),
+             lambda: engine.fuzzy_find(short, candidates, indices[:4], device=gpu, starts=True)]
+
+    _, _, offsets = candidates._device
+    kept = offsets[6].clone()
+    offsets[6] = offsets[5] - 3  # candidate 5 now "ends" before it begins; every other string still lies inside the tape
+    for call in calls:
+        with pytest.raises(szs.StringZillasError) as refused:
+            call()
+        assert refused.value.status_name == "unexpected_dimensions" and "ascend" in str(refused.value).lower(), str(refused.value)
+    offsets[6] = kept
+
+    assert np.array_equal(calls[0](), expected(oracle.levenshtein(queries, plain), indices))  # the engine goes on
+    distances, starts, ends = listed(dense(short, plain), indices[:4])
+    assert same(calls[1](), (distances, ends))
+    assert same(calls[2](), (distances, starts, ends))
+
+
 def test_an_index_past_the_end_is_refused(gpu):
     import torch
 
