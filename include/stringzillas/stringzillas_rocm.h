@@ -21,6 +21,8 @@
  *  - szs_rocm_fuzzy_find*       : the best match of a query INSIDE each listed candidate - fewest edits to some substring, and where it
  *    ends - for a snippet in a document, a primer in a read, a misspelled name in a record (csrc/host/fuzzy_find.c).
  *  - szs_rocm_fuzzy_find_spans* : the same call with the whole span: where that best match starts as well.
+ *  - szs_rocm_fuzzy_search*     : the k candidates of a corpus that contain the best such match per query, without the matrix
+ *    (csrc/host/fuzzy_search.c); szs_rocm_fuzzy_search_probe reports how a call would be cut.
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -240,6 +242,58 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_spans_u64tape(void *engine, szs_d
                                                              sz_size_t row_stride, char const **error_message);
 
 /**
+ *  Fuzzy SEARCH: which candidates of a corpus contain something close to the query?  Row q receives the k candidates with the
+ *  smallest szs_rocm_fuzzy_find distance of queries[q] - min over j of D[m][j], free start in the text - in ascending order, ties
+ *  to the LOWER candidate index (szs_rocm_top_k's rule, from the same scan):
+ *      indices[q * row_stride + i], distances[q * row_stride + i] for i < k, and - where the arrays are given -
+ *      ends[q * row_stride + i], starts[q * row_stride + i]: exactly what szs_rocm_fuzzy_find / szs_rocm_fuzzy_find_spans return for
+ *      the pair (q, indices[q * row_stride + i]), bit for bit.
+ *  Cells [k, row_stride) are left untouched.  No queries x candidates matrix is written anywhere the caller sees: the call scores
+ *  tiles of (a block of queries) x (up to 2^18 candidates) into device scratch with csrc/hip/myers_fuzzy_tile.hip - one workgroup
+ *  per (query, segment of the tile's candidates), so a few queries over a large corpus fill the device - and folds every tile into
+ *  per-query lists with csrc/hip/top_k.hip.  `ends` and `starts` come from a winners pass: szs_rocm_fuzzy_find's kernels on the
+ *  k listed candidates of every row; a call without `ends` launches none.
+ *
+ *  `candidates` NULL: SELF-SEARCH - the queries in each other, each query's own index excluded.  A row with fewer than k candidates
+ *  (none at all; the self-search of one query) is completed with index SZ_SIZE_MAX, distance 0, end 0, start 0.  A query of no
+ *  bytes has distance 0 and end 0 in every candidate: its row lists candidates 0 ... k - 1.
+ *
+ *  1 <= k <= 1024 and row_stride >= k, else sz_unexpected_dimensions_k - checked first.  `engine` must be a unit-cost BYTE
+ *  Levenshtein engine, as for szs_rocm_fuzzy_find: any other, a blank or a NULL one is refused with sz_status_unknown_k.  Zero
+ *  queries: success, nothing is looked at.  `indices` and `distances` are required, `ends` is optional, `starts` requires `ends`: a
+ *  missing one is refused with sz_status_unknown_k.  A query of more than 256 bytes fails the whole call with
+ *  sz_unexpected_dimensions_k before anything is launched.  Nothing is written on a refusal.  The outputs may live in device,
+ *  pinned, unified or plain host memory (staged densely, one 2-D copy per array), the strings' offsets likewise; the strings
+ *  themselves must be readable by the device.  Synchronous, also when it fails.
+ *
+ *  Knobs, none of which changes a result: `top_k_tile` caps the candidates of a tile, `fuzzy_search_segment` sets the candidates one
+ *  workgroup scores for its row (rounded up to a multiple of 64; automatic: enough workgroups to fill the device four times over).
+ *  szs_rocm_last_call_profile: pairs and cells of every scored (query, candidate) - the self column included - plus the winners
+ *  pass's; launches = scoring, scan / fold, emit and winners-pass launches; kernel time = the scoring launches.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                                 sz_sequence_t const *candidates, sz_size_t k, sz_size_t *indices, sz_size_t *distances,
+                                                 sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                         sz_sequence_u32tape_t const *candidates, sz_size_t k, sz_size_t *indices,
+                                                         sz_size_t *distances, sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride,
+                                                         char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                         sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices,
+                                                         sz_size_t *distances, sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride,
+                                                         char const **error_message);
+
+/**
+ *  How szs_rocm_fuzzy_search would cut a call of these counts - host only, no GPU: the queries of a block, the candidates of a tile,
+ *  the candidates one workgroup of the tile kernel scores for its row (`segment`, a multiple of 64) and the workgroups of the first
+ *  tile's launch = rows of the block x ceil(tile / segment).  The knobs apply as they do to the call.  Outputs are optional.
+ *  k outside [1, 1024] or `longest_query` above 256: sz_unexpected_dimensions_k.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_probe(sz_size_t queries_count, sz_size_t candidates_count, sz_size_t k,
+                                                       sz_size_t longest_query, sz_size_t *block, sz_size_t *tile, sz_size_t *segment,
+                                                       sz_size_t *workgroups);
+
+/**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine
  *  - it supplies `dimensions` and owns the device scratch; any other handle is refused and nothing is written.  Hash matrices are
  *  row-major `sz_u32_t` with a row stride in BYTES, a multiple of 4 and at least 4 * dimensions, exactly as `szs_fingerprints_*`
@@ -437,6 +491,8 @@ SZ_API_RUNTIME sz_status_t szs_rocm_node_scores_u64tape(szs_rocm_node_engine_t e
  *  "rerank" (0: every row of a rerank call as an engine call of its own | 1: rows whose query has at most 256 bytes in one launch of
  *  hip/myers_rerank.hip, longer rows as engine calls; automatic: those, and rows whose query has at most 64 KiB in one launch of
  *  hip/myers_rerank_strips.hip),
+ *  "fuzzy_search_segment" (n: the candidates one workgroup of hip/myers_fuzzy_tile.hip scores for its row in a fuzzy search, rounded
+ *  up to a multiple of 64; automatic: enough workgroups to fill the device four times over),
  *  "queues" (see below), "roctx" (1: the host phases of every call - plan, decide, enqueue, wait - as roctx ranges for a
  *  `rocprofv3 --marker-trace` timeline; the marker library is looked up at run time, never linked),
  *  "cpu_requests" (strict | gpu: serve capability

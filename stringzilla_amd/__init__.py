@@ -486,6 +486,58 @@ class _Engine:
         host = results[:, :rows].cpu().numpy() if isinstance(results, torch.Tensor) else results[:, :rows, :k]
         return tuple(matrix.view(np.uint64) for matrix in host)
 
+    def fuzzy_search(self, queries, candidates=None, k=16, device: Optional[DeviceScope] = None, out=None, starts=False):
+        """The `k` candidates that contain the best approximate match of every query (`szs_rocm_fuzzy_search_*`): returns
+        `(indices, distances, ends)`, three `uint64` `(rows, k)` NumPy matrices - row `q` lists the candidates with the smallest
+        `fuzzy_find` distance of `queries[q]`, ascending, ties to the lower index; `distances` and `ends` are what `fuzzy_find` returns
+        for those pairs.  `starts=True`: `(indices, distances, starts, ends)`, as `fuzzy_find(..., starts=True)` returns them.
+        `candidates` None: self-search, each query's own index excluded.  A row with fewer than `k` candidates ends in index
+        2**64 - 1 and zeros.  `out`: a triple - with `starts` a 4-tuple - of NumPy arrays or torch tensors of 8-byte cells in that
+        order, of one row stride, filled and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes."""
+        import torch
+
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
+            raise ValueError(f"k must be an integer within [1, 1024], got {k!r}")
+        k = int(k)
+        names = ("out indices", "out distances", "out starts", "out ends") if starts else ("out indices", "out distances", "out ends")
+        queries = _as_strs(queries)
+        candidates = None if candidates is None else _as_strs(candidates)
+        rows = len(queries)
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != len(names):
+                raise ValueError(f"`out` must be a tuple of {len(names)} matrices: {', '.join(name[4:] for name in names)}")
+            pointers, stride = [], None
+            for matrix, name in zip(out, names):
+                pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
+                if stride is not None and own_stride != stride:
+                    raise ValueError("the matrices of `out` must share one row stride")
+                stride = own_stride
+                pointers.append(pointer)
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        for matrix, name in (tuple(zip(out, names)) if out is not None else ()):
+            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
+                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
+        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
+            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        if out is None:
+            results = torch.empty((len(names), max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+            pointers, stride = [matrix.data_ptr() for matrix in results], k
+        indices_pointer, distances_pointer, ends_pointer = pointers[0], pointers[1], pointers[-1]
+        starts_pointer = pointers[2] if starts else None
+
+        error = ctypes.c_char_p()
+        call = lib.szs_rocm_fuzzy_search_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_search_u32tape
+        q_tape = queries._tape(gpu_device)
+        c_tape = None if candidates is None else candidates._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape), k,
+                      indices_pointer, distances_pointer, starts_pointer, ends_pointer, stride, ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        return tuple(matrix.view(np.uint64) for matrix in results[:, :rows].cpu().numpy())
+
     def __del__(self):
         handle = getattr(self, "handle", None)
         if handle and self._free is not None:

@@ -85,6 +85,7 @@ _TOP_K = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_
 _RERANK = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ERR])
 _FUZZY_FIND = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ERR])
 _FUZZY_FIND_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
+_FUZZY_SEARCH = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 
 SIGNATURES = {
     "szs_version_major": (c_int, []), "szs_version_minor": (c_int, []), "szs_version_patch": (c_int, []),
@@ -140,6 +141,9 @@ SIGNATURES = {
     "szs_rocm_fuzzy_find": _FUZZY_FIND, "szs_rocm_fuzzy_find_u32tape": _FUZZY_FIND, "szs_rocm_fuzzy_find_u64tape": _FUZZY_FIND,
     "szs_rocm_fuzzy_find_spans": _FUZZY_FIND_SPANS, "szs_rocm_fuzzy_find_spans_u32tape": _FUZZY_FIND_SPANS,
     "szs_rocm_fuzzy_find_spans_u64tape": _FUZZY_FIND_SPANS,
+    "szs_rocm_fuzzy_search": _FUZZY_SEARCH, "szs_rocm_fuzzy_search_u32tape": _FUZZY_SEARCH, "szs_rocm_fuzzy_search_u64tape": _FUZZY_SEARCH,
+    "szs_rocm_fuzzy_search_probe": (c_int, [c_size_t, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                            ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "szs_rocm_rerank_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "szs_rocm_fingerprint_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t,
                                              c_void_p, c_size_t, ERR]),
@@ -186,7 +190,8 @@ _KNOBS = {"tier": "SZS_ROCM_TIER", "swap": "SZS_ROCM_SWAP", "packed": "SZS_ROCM_
           "team": "SZS_ROCM_TEAM", "queues": "SZS_ROCM_QUEUES", "roctx": "SZS_ROCM_ROCTX",
           "queue": "SZS_ROCM_QUEUE", "queue_words": "SZS_ROCM_QUEUE_WORDS", "queue_rounds": "SZS_ROCM_QUEUE_ROUNDS",
           "queue_priority": "SZS_ROCM_QUEUE_PRIORITY", "fused": "SZS_ROCM_FUSED", "tiny": "SZS_ROCM_TINY",
-          "top_k_tile": "SZS_ROCM_TOP_K_TILE", "rerank": "SZS_ROCM_RERANK"}
+          "top_k_tile": "SZS_ROCM_TOP_K_TILE", "rerank": "SZS_ROCM_RERANK",
+          "fuzzy_search_segment": "SZS_ROCM_FUZZY_SEARCH_SEGMENT"}
 _knob_values = {name: os.environ.get(variable) for name, variable in _KNOBS.items()}  # what the library read when it was loaded
 
 
@@ -216,6 +221,18 @@ def rerank_probe(query_lengths, k, longest_candidate, unit_cost=True, runes=Fals
     if status != 0:
         raise StringZillasError(status, None)
     return routes, strips, strip_words, int(scratch.value)
+
+
+def fuzzy_search_probe(queries_count, candidates_count, k, longest_query=0):
+    """`szs_rocm_fuzzy_search_probe`: how a fuzzy search of these counts would be cut - no GPU involved.  Returns (block, tile, segment,
+    workgroups): the queries of a block, the candidates of a tile, the candidates one workgroup of the tile kernel scores for its row
+    and the workgroups of the first tile's launch.  The `top_k_tile` and `fuzzy_search_segment` knobs apply as they do to the call."""
+    block, tile, segment, workgroups = c_size_t(0), c_size_t(0), c_size_t(0), c_size_t(0)
+    status = lib.szs_rocm_fuzzy_search_probe(queries_count, candidates_count, k, longest_query, ctypes.byref(block), ctypes.byref(tile),
+                                             ctypes.byref(segment), ctypes.byref(workgroups))
+    if status != 0:
+        raise StringZillasError(status, None)
+    return int(block.value), int(tile.value), int(segment.value), int(workgroups.value)
 
 
 PAIR_RULE_CHOOSE = 0xFFFFFFFF

@@ -347,6 +347,18 @@ int szs_hip_levenshtein_fuzzy_starts(szs_rerank_side_t const *queries, szs_reran
                                      uint64_t outputs_stride, unsigned widest, uint32_t *flags, unsigned long long *counters,
                                      void *stream);
 
+/**
+ *  A tile of the same distance for the search (hip/myers_fuzzy_tile.hip; host/fuzzy_search.c):
+ *  cells[r * cells_stride + c] = the distance of query first_query + r inside candidate first_column + c, for r < rows and c < columns,
+ *  8-byte cells that szs_hip_top_k_scan folds unchanged with `descending` = 0.  One one-wavefront workgroup per (row, `segment`
+ *  columns of the tile): `segment` is a multiple of 64, the grid rows x ceil(columns / segment) on x.  Every cell is written; a query
+ *  of no bytes scores 0 everywhere.  Queries of more than 256 bytes set `flags[SZS_RERANK_FLAG_UNFIT]`, offsets that descend
+ *  `flags[SZS_RERANK_FLAG_TAPE]`; sides, flags and counters as above.  Rows or columns beyond a side's count are refused.
+ */
+int szs_hip_levenshtein_fuzzy_tile(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,
+                                   uint32_t rows, uint64_t first_column, uint32_t columns, uint32_t segment, uint64_t *cells,
+                                   uint64_t cells_stride, uint32_t *flags, unsigned long long *counters, void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {
@@ -383,6 +395,8 @@ enum {
     szs_knob_rerank_k,      /* -1 automatic (rows of a unit-cost byte engine: a query of at most 256 bytes by hip/myers_rerank.hip, one of
                                at most 64 KiB by hip/myers_rerank_strips.hip) | 0: every row of a rerank call as an engine call of its
                                own (host/rerank.c) | 1: the short kernel only, longer rows as engine calls (the A/B leg of the strips) */
+    szs_knob_fuzzy_search_segment_k, /* -1 automatic | n: the candidates one workgroup of hip/myers_fuzzy_tile.hip scores for its row,
+                                        rounded up to a multiple of 64 (host/fuzzy_search.c) */
     szs_knob_count_k
 };
 int szs_tuning_get(int knob);

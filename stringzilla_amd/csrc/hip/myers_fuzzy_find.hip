@@ -3,7 +3,8 @@
  *  section 4.9): distance = min over j of D[m][j] of the unit-cost DP whose row zero is all zeros (a free start in the text), and
  *  end = the smallest j that attains it.
  *
- *  Groups, rows, tables, indices, flags, the text walk and the counters are hip/rerank_core.hpp's.  This kernel's own:
+ *  Groups, rows, tables, indices, flags, the text walk and the counters are hip/rerank_core.hpp's.  The table and the walk of a lane
+ *  (hip/fuzzy_core.hpp: shared with hip/myers_fuzzy_tile.hip) are this distance's own:
  *
  *  - The column is myers_infix_column (hip/myers_core.hpp): nothing enters bit 0, and the horizontal pair of the pattern's last row
  *    comes back.  The pattern is right-aligned, so that row is bit 31 of word W - 1 for every row of the wavefront.
@@ -15,7 +16,7 @@
  *    score moves `best` and `end` (the leftmost end).  A live lane stores both as ordinary 8-byte vector stores.
  *  - `indices` NULL is the dense form: slot r is candidate r.
  */
-#include "rerank_core.hpp"
+#include "fuzzy_core.hpp"
 
 namespace szs_hip {
 
@@ -24,8 +25,7 @@ __device__ __forceinline__ void fuzzy_find_rows(u32 *table, listed_row_t const &
                                                 u64 const *__restrict__ indices, u64 indices_stride, u64 k, u64 *__restrict__ distances,
                                                 u64 *__restrict__ ends, u64 outputs_stride, u32 *flags, unsigned long long *counters) {
     u32 const sub = threadIdx.x % lanes_;
-    u32 const pad = 32u * words_ - row.query_length; // phantom low rows of THIS row (a row without a query: all of them)
-    listed_table<words_, lanes_>(table, row, [&](int w) { return rerank_bits_in_word(0, pad, w); }, [&](u32 i) { return pad + i; });
+    fuzzy_table<words_, lanes_>(table, row);
 
     listed_counters_t counted;
 #pragma unroll 1
@@ -41,20 +41,8 @@ __device__ __forceinline__ void fuzzy_find_rows(u32 *table, listed_row_t const &
                           listed_candidate(candidates, indices ? indices[row.row * indices_stride + rank] : rank, on_empty, flags, address,
                                            text_length);
 
-        u32 vp[words_], vn[words_];
-#pragma unroll
-        for (int w = 0; w < words_; ++w) vp[w] = rerank_bits_in_word(pad, 32u * words_, w), vn[w] = 0;
-        u32 score = row.query_length, best = row.query_length, end = 0;
-        listed_walk(
-            text_stream_t(address, text_length), text_length, live,
-            [&](u32 symbol, u32 column_end) {
-                u32 eq[words_];
-                load_match_masks<words_, byte_rows_k>(table, symbol, eq);
-                u32 const top = myers_infix_column<words_>(vp, vn, eq);
-                score += (top & 1u) - (top >> 1);
-                if (score < best) best = score, end = column_end; // strictly smaller: the leftmost end
-            },
-            []() { return true; });
+        u32 best, end;
+        fuzzy_best_match<words_>(table, row.query_length, address, text_length, live, best, end);
 
         if (live) {
             distances[at] = best;

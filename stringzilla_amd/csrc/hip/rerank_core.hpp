@@ -1,6 +1,8 @@
 /*
  *  rerank_core.hpp - what a kernel over LISTED pairs is: the scaffold of hip/myers_rerank.hip (queries of up to 256 bytes in one
  *  bit-vector), hip/myers_rerank_strips.hip (longer queries as strips), hip/myers_fuzzy_find.hip and hip/myers_fuzzy_spans.hip.
+ *  hip/myers_fuzzy_tile.hip takes the pieces - rows, widths, tables, candidates, the walk, the counters - for a grid of its own: one
+ *  row and a run of consecutive candidates per workgroup.
  *
  *  - A GROUP of L = 16 / 32 / 64 lanes (the smallest that holds min(k, 64): szs_hip_rerank_lanes) serves one row - one query and
  *    the k candidates an index row names: its own Peq table in LDS (peq_layout<W, 256>), one listed candidate per lane, fetched
@@ -71,19 +73,27 @@ struct listed_row_t {
     u32 query_length;
 };
 
-/** The row in slot `slot` of `rows`: slot -> row -> query.  A query beyond the side, or one whose offsets descend, raises the TAPE
- *  flag; one of more than `longest_allowed` bytes the UNFIT flag (the host's job to prevent).  Either way the group has no row. */
-__device__ __forceinline__ listed_row_t listed_row(szs_rerank_side_t const &queries, u64 first_query, u32 const *__restrict__ rows,
-                                                   u32 rows_count, u64 slot, u32 longest_allowed, u32 *flags) {
-    listed_row_t found = {slot < rows_count, 0, 0, 0};
+/** The row of a group, row -> query: `row_of()` names it where the group `has_row`.  A query beyond the side, or one whose offsets
+ *  descend, raises the TAPE flag; one of more than `longest_allowed` bytes the UNFIT flag (the host's job to prevent).  Either way the
+ *  group has no row. */
+template <typename row_of_t>
+__device__ __forceinline__ listed_row_t listed_row(szs_rerank_side_t const &queries, u64 first_query, bool has_row, row_of_t row_of,
+                                                   u32 longest_allowed, u32 *flags) {
+    listed_row_t found = {has_row, 0, 0, 0};
     if (!found.has_row) return found;
-    found.row = rows[slot];
+    found.row = row_of();
     u64 const query = first_query + found.row;
     if (query >= queries.count || !rerank_fetch(queries, query, found.query_address, found.query_length))
         flags[SZS_RERANK_FLAG_TAPE] = 1u, found.has_row = false;
     else if (found.query_length > longest_allowed) flags[SZS_RERANK_FLAG_UNFIT] = 1u, found.has_row = false;
     if (!found.has_row) found.query_length = 0;
     return found;
+}
+
+/** The row in slot `slot` of `rows`: slot -> row -> query. */
+__device__ __forceinline__ listed_row_t listed_row(szs_rerank_side_t const &queries, u64 first_query, u32 const *__restrict__ rows,
+                                                   u32 rows_count, u64 slot, u32 longest_allowed, u32 *flags) {
+    return listed_row(queries, first_query, slot < rows_count, [&]() { return rows[slot]; }, longest_allowed, flags);
 }
 
 /** The longest query of the wavefront's rows - a scalar, so one of the eight bodies runs and nothing diverges. */

@@ -419,6 +419,35 @@ sz_status_t szs_rocm_fuzzy_find_spans_u64tape(void *engine, szs_device_scope_t d
     SZS_FUZZY_FIND_SPANS_BODY(input_from_u64tape)
 }
 
+/* ---- fuzzy search (host/fuzzy_search.c) ------------------------------------------------------------------------------- */
+
+#define SZS_FUZZY_SEARCH_BODY(MAKE_INPUT)                                                                              \
+    if (k < 1 || k > SZS_TOP_K_MOST || row_stride < k || !queries)                                                     \
+        return szs_engine_fuzzy_search((szs_engine_s *)engine, (szs_scope_s *)device, NULL, NULL, k, indices,          \
+                                       distances, starts, ends, row_stride, error_message);                            \
+    szs_input_t const query_input = MAKE_INPUT(queries);                                                               \
+    szs_input_t candidate_input;                                                                                       \
+    if (candidates) candidate_input = MAKE_INPUT(candidates);                                                          \
+    return szs_engine_fuzzy_search((szs_engine_s *)engine, (szs_scope_s *)device, &query_input,                        \
+                                   candidates ? &candidate_input : NULL, k, indices, distances, starts, ends,          \
+                                   row_stride, error_message);
+
+sz_status_t szs_rocm_fuzzy_search(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, sz_sequence_t const *candidates,
+                                  sz_size_t k, sz_size_t *indices, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                  sz_size_t row_stride, char const **error_message) {
+    SZS_FUZZY_SEARCH_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_fuzzy_search_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                          sz_sequence_u32tape_t const *candidates, sz_size_t k, sz_size_t *indices, sz_size_t *distances,
+                                          sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride, char const **error_message) {
+    SZS_FUZZY_SEARCH_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_fuzzy_search_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                          sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices, sz_size_t *distances,
+                                          sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride, char const **error_message) {
+    SZS_FUZZY_SEARCH_BODY(input_from_u64tape)
+}
+
 /* ---- fingerprint search (host/fingerprint_search.c) ------------------------------------------------------------------- */
 
 sz_status_t szs_rocm_fingerprint_matches(szs_fingerprints_t engine, szs_device_scope_t device, sz_u32_t const *query_hashes,

@@ -15,17 +15,9 @@
 
 static char const fuzzy_find_long_query[] = "A query of more than 256 bytes: beyond what fuzzy find takes";
 
-/** What the blocks of one call share. */
-typedef struct {
-    szs_listed_call_t listed;
-    uint64_t const *indices; /* NULL: the dense form */
-    uint64_t *distances, *ends, *starts; /* `starts` NULL: the plain call - one launch a block */
-    int stage_indices, stage_distances, stage_ends, stage_starts;
-} szs_fuzzy_find_call_t;
-
 /** One block: stages what the device cannot reach, launches the kernel once over every row - and the kernel of the starts behind it,
  *  where the call asks for them - brings the outputs home, reads the flags. */
-static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size_t rows, hipError_t *hip_error, char const **error_message) {
+sz_status_t szs_fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size_t rows, hipError_t *hip_error, char const **error_message) {
     szs_listed_call_t *const listed = &call->listed;
     hipStream_t const stream = listed->stream;
     size_t const k = listed->k, row_stride = listed->row_stride, row_bytes = k * sizeof(uint64_t), pitch = row_stride * sizeof(uint64_t);
@@ -76,6 +68,34 @@ static sz_status_t fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size
                                    fuzzy_find_long_query, error_message);
 }
 
+size_t szs_fuzzy_find_stage(szs_fuzzy_find_call_t *call) {
+    call->stage_indices = call->indices && !szs_classify_pointer(call->indices).device_accessible;
+    call->stage_distances = !szs_classify_pointer(call->distances).device_accessible;
+    call->stage_ends = call->ends && !szs_classify_pointer(call->ends).device_accessible;
+    call->stage_starts = call->starts && !szs_classify_pointer(call->starts).device_accessible;
+    int const dense_outputs = call->stage_distances || call->stage_ends || call->stage_starts;
+    return (size_t)call->stage_indices + (dense_outputs ? 1 + (call->ends != NULL) + (call->starts != NULL) : 0);
+}
+
+sz_status_t szs_fuzzy_find_prepare(szs_fuzzy_find_call_t *call, szs_input_t const *queries, szs_input_t const *candidates,
+                                   char const *long_query, char const **error_message) {
+    szs_listed_call_t *const listed = &call->listed;
+    int usable = 0;
+    sz_status_t status = szs_listed_prepare_queries(listed, queries, SZS_RERANK_LONGEST_QUERY, &usable, error_message);
+    if (status != sz_success_k) return status;
+    if (!usable) return szs_report(sz_status_unknown_k, error_message, "The queries are not strings the device can read");
+    /* a query beyond the kernel's bit-vector fails the call here, before anything is launched */
+    for (size_t q = 0; q < queries->count; ++q) {
+        if (listed->query_lengths[q] != ~0u) continue;
+        int const descends = !listed->refs_needed[0] && szs_tape_offset(queries, listed->offsets[0], q + 1) < szs_tape_offset(queries, listed->offsets[0], q);
+        return szs_report(sz_unexpected_dimensions_k, error_message, descends ? "Tape offsets must ascend" : long_query);
+    }
+    status = szs_listed_prepare_candidates(listed, candidates, &usable, error_message);
+    if (status != sz_success_k) return status;
+    if (!usable) return szs_report(sz_status_unknown_k, error_message, "The candidates are not strings the device can read");
+    return sz_success_k;
+}
+
 /** The one call path.  `starts` set: the starts are computed too.  `missing`: the message for a required output that is NULL, refused
  *  behind the checks of the dimensions, the engine and an empty batch; NULL when the entry has all it requires. */
 static sz_status_t fuzzy_find_call(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
@@ -109,12 +129,7 @@ static sz_status_t fuzzy_find_call(szs_engine_s *engine, szs_scope_s *scope, szs
     if (status != sz_success_k) return status;
 
     /* blocks of rows: the kernel's row list and - where the device cannot reach the caller's arrays - their dense copies in budget */
-    call.stage_indices = indices && !szs_classify_pointer(indices).device_accessible;
-    call.stage_distances = !szs_classify_pointer(distances).device_accessible;
-    call.stage_ends = ends && !szs_classify_pointer(ends).device_accessible;
-    call.stage_starts = starts && !szs_classify_pointer(starts).device_accessible;
-    int const dense_outputs = call.stage_distances || call.stage_ends || call.stage_starts;
-    size_t const staged_arrays = (size_t)call.stage_indices + (dense_outputs ? 1 + (ends != NULL) + (starts != NULL) : 0);
+    size_t const staged_arrays = szs_fuzzy_find_stage(&call);
     size_t const block = listed->block = szs_listed_block_rows(q_count, k, staged_arrays != 0);
 
     size_t const no_extras[2] = {0, 0};
@@ -122,23 +137,12 @@ static sz_status_t fuzzy_find_call(szs_engine_s *engine, szs_scope_s *scope, szs
     status = szs_listed_reserve(listed, queries, candidates, 1, no_extras, no_extras, staged_arrays, extras, error_message);
     if (status != sz_success_k) return status;
 
-    int usable = 0;
-    status = szs_listed_prepare_queries(listed, queries, SZS_RERANK_LONGEST_QUERY, &usable, error_message);
+    status = szs_fuzzy_find_prepare(&call, queries, candidates, fuzzy_find_long_query, error_message);
     if (status != sz_success_k) return status;
-    if (!usable) return szs_report(sz_status_unknown_k, error_message, "The queries are not strings the device can read");
-    /* a query beyond the kernel's bit-vector fails the call here, before anything is launched */
-    for (size_t q = 0; q < q_count; ++q) {
-        if (listed->query_lengths[q] != ~0u) continue;
-        int const descends = !listed->refs_needed[0] && szs_tape_offset(queries, listed->offsets[0], q + 1) < szs_tape_offset(queries, listed->offsets[0], q);
-        return szs_report(sz_unexpected_dimensions_k, error_message, descends ? "Tape offsets must ascend" : fuzzy_find_long_query);
-    }
-    status = szs_listed_prepare_candidates(listed, candidates, &usable, error_message);
-    if (status != sz_success_k) return status;
-    if (!usable) return szs_report(sz_status_unknown_k, error_message, "The candidates are not strings the device can read");
 
     hipError_t error = hipSuccess;
     for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block)
-        status = fuzzy_find_block(&call, q0, q_count - q0 < block ? q_count - q0 : block, &error, error_message);
+        status = szs_fuzzy_find_block(&call, q0, q_count - q0 < block ? q_count - q0 : block, &error, error_message);
     hipError_t const drained = hipStreamSynchronize(listed->stream); /* synchronous, also when it fails */
     if (status != sz_success_k) return status;
     if (error == hipSuccess) error = drained;

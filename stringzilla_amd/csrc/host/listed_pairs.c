@@ -185,7 +185,7 @@ sz_status_t szs_listed_prepare_candidates(szs_listed_call_t *call, szs_input_t c
 hipError_t szs_listed_block_begin(szs_listed_call_t *call, size_t dealt, hipError_t error) {
     memset(call->flags, 0, SZS_RERANK_FLAGS * sizeof(uint32_t));
     if (error == hipSuccess) error = hipMemsetAsync(call->device_counters, 0, 3 * sizeof(uint64_t), call->stream);
-    if (error == hipSuccess)
+    if (error == hipSuccess && dealt) /* (none: a launch that takes no row list - the search's tile) */
         error = hipMemcpyAsync(call->device_order, call->order, dealt * sizeof(uint32_t), hipMemcpyHostToDevice, call->stream);
     if (error == hipSuccess) error = hipEventRecord(call->engine->event_start, call->stream);
     return error;

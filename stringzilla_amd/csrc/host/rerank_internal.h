@@ -1,6 +1,6 @@
 /*
  *  rerank_internal.h - what the calls over LISTED pairs share on the host (rerank.c: szs_rocm_rerank*; fuzzy_find.c:
- *  szs_rocm_fuzzy_find*): the block and staging budgets, the deal of a block's rows by descending query length, and the skeleton of
+ *  szs_rocm_fuzzy_find*; fuzzy_search.c: szs_rocm_fuzzy_search*, for its strings and its winners): the block and staging budgets, the deal of a block's rows by descending query length, and the skeleton of
  *  such a call (listed_pairs.c): its preamble, the validation of indices, the scratch, the two sides as the kernels read them, and
  *  the bracket around a block's launches.  Policy stays with the callers: which engines, which lengths, what an unusable side means.
  */
@@ -93,6 +93,26 @@ hipError_t szs_listed_block_begin(szs_listed_call_t *call, size_t dealt, hipErro
 hipError_t szs_listed_block_end(szs_listed_call_t *call, hipError_t error);
 sz_status_t szs_listed_block_finish(szs_listed_call_t *call, hipError_t error, hipError_t *hip_error, unsigned launches, uint32_t longest,
                                     size_t bytes_per_pair, sz_status_t unfit_status, char const *unfit_message, char const **error_message);
+
+/* ---- fuzzy find's own steps (fuzzy_find.c), which the search (fuzzy_search.c) runs on the rows it has found ---------------------- */
+
+/** What the blocks of one fuzzy-find call share. */
+typedef struct {
+    szs_listed_call_t listed;
+    uint64_t const *indices; /* NULL: the dense form */
+    uint64_t *distances, *ends, *starts; /* `starts` NULL: the plain call - one launch a block */
+    int stage_indices, stage_distances, stage_ends, stage_starts;
+} szs_fuzzy_find_call_t;
+
+/** Which of the call's arrays the device cannot reach (`stage_*`), from its pointers; returns the dense block x k copies they take. */
+size_t szs_fuzzy_find_stage(szs_fuzzy_find_call_t *call);
+/** Both sides as the kernels read them.  A query of more than SZS_RERANK_LONGEST_QUERY bytes (`long_query`: the message), offsets that
+ *  descend and strings the device cannot read fail the call here, before anything is launched. */
+sz_status_t szs_fuzzy_find_prepare(szs_fuzzy_find_call_t *call, szs_input_t const *queries, szs_input_t const *candidates,
+                                   char const *long_query, char const **error_message);
+/** Rows [q0, q0 + rows) - at most `listed.block` - of the call: one launch of hip/myers_fuzzy_find.hip, with `starts` the launch of
+ *  hip/myers_fuzzy_spans.hip behind it; drains the stream and adds the block to `listed.total`. */
+sz_status_t szs_fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size_t rows, hipError_t *hip_error, char const **error_message);
 
 /**
  *  The rows of a block whose query has at most SZS_RERANK_LONGEST_QUERY bytes into `order`, longest query first (a counting sort of

@@ -156,7 +156,8 @@ typedef struct szs_engine_s {
     szs_buffer_t device_top_k_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
     szs_buffer_t device_top_k_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
 
-    /* rerank calls (host/rerank.c); fuzzy-find calls (host/fuzzy_find.c) lay their own parts out in the same buffers */
+    /* rerank calls (host/rerank.c); fuzzy-find calls (host/fuzzy_find.c) lay their own parts out in the same buffers, and so does a
+     * fuzzy search (host/fuzzy_search.c), which scores into the top-k buffers above */
     szs_buffer_t host_rerank_offsets[2]; /* host: tape offsets only the device can read - queries, candidates */
     szs_buffer_t host_rerank;            /* host: query lengths, gathered strings, a block of indices only the device can read, a row's picks */
     szs_buffer_t pinned_rerank;          /* pinned: the kernel's flag, its counters, a row's cells and image, the kernel's rows, refs of both sides */
@@ -402,5 +403,14 @@ sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_
 sz_status_t szs_engine_fuzzy_find_spans(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                                         size_t const *indices, size_t k, size_t *distances, size_t *starts, size_t *ends,
                                         size_t row_stride, char const **error_message);
+
+/* ---- fuzzy search (fuzzy_search.c) -------------------------------------------------------------------------------------- */
+
+/** The k candidates with the smallest fuzzy-find distance per query; `candidates` NULL: self-search (each query in all queries but
+ *  itself); `ends` may be NULL, `starts` needs `ends`.  Unit-cost byte Levenshtein engines only.  Uses the engine's top-k and rerank
+ *  buffers. */
+sz_status_t szs_engine_fuzzy_search(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                    size_t k, size_t *indices, size_t *distances, size_t *starts, size_t *ends, size_t row_stride,
+                                    char const **error_message);
 
 #endif /* SZS_INTERNAL_H_ */

@@ -46,6 +46,7 @@ static struct {
     [szs_knob_tiny_k] = {"tiny", "SZS_ROCM_TINY"},
     [szs_knob_top_k_tile_k] = {"top_k_tile", "SZS_ROCM_TOP_K_TILE"},
     [szs_knob_rerank_k] = {"rerank", "SZS_ROCM_RERANK"},
+    [szs_knob_fuzzy_search_segment_k] = {"fuzzy_search_segment", "SZS_ROCM_FUZZY_SEARCH_SEGMENT"},
 };
 
 /** Text -> value.  -1 always means "automatic".  Tier names: lanes 0, systolic 1, chain 2; planner: host 0, device 1. */
