@@ -27,14 +27,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
-
-static double now_milliseconds(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
 szs_pointer_traits_t szs_classify_pointer(void const *pointer) {
     szs_pointer_traits_t traits = {1, 0, 0};
     if (!pointer) return traits;
@@ -273,9 +265,7 @@ static void release_device_state(szs_engine_s *engine) {
     szs_buffer_release(&engine->pinned_summary);
     szs_buffer_release(&engine->pinned_squares);
     szs_buffer_release(&engine->device_fused);
-    szs_buffer_release(&engine->device_top_k_scratch);
-    szs_buffer_release(&engine->device_top_k_lists);
-    szs_buffer_release(&engine->device_top_k_out);
+    szs_selection_release(&engine->selection);
     szs_buffer_release(&engine->pinned_rerank);
     szs_buffer_release(&engine->device_rerank);
     szs_buffer_release(&engine->device_rerank_staged);
@@ -860,7 +850,7 @@ void szs_call_phase(szs_call_t *call, int index) {
         else call->ranges = 1;
     }
     if (!call->trace) return;
-    double const now = now_milliseconds();
+    double const now = szs_now_milliseconds();
     call->phases[index] += now - call->phase_started, call->phase_started = now;
 }
 
@@ -921,7 +911,7 @@ sz_status_t szs_call_finish(szs_call_t *call, szs_decision_t const *d, hipError_
     profile->queue_items = engine->last_queued ? d->queue.items_total : 0, profile->queue_tiles = profile->queue_items ? d->queue.tiles_count : 0;
     engine->last_queued = 0;
     profile->longest_query = d->longest[0], profile->longest_candidate = d->longest[1];
-    profile->host_milliseconds = now_milliseconds() - call->started;
+    profile->host_milliseconds = szs_now_milliseconds() - call->started;
     szs_call_phase(call, 5);
 #ifdef SZS_PLAN_TIMESTAMPS
     if (call->trace) {
@@ -1209,7 +1199,7 @@ sz_status_t szs_engine_cross(szs_engine_s *engine, szs_scope_s *scope, szs_input
                              char const **error_message) {
     szs_call_t call;
     memset(&call, 0, sizeof(call));
-    call.started = call.phase_started = now_milliseconds();
+    call.started = call.phase_started = szs_now_milliseconds();
     call.trace = szs_tuning_get(szs_knob_trace_k) > 0; /* per-phase host times of every call on stderr (a measuring aid) */
     if (!engine || engine->magic != SZS_ENGINE_MAGIC)
         return szs_report(sz_status_unknown_k, error_message, "Engine must be initialized");

@@ -84,9 +84,7 @@ static void release_device_state(szs_fingerprints_s *engine) {
     szs_buffer_release(&engine->device_partials);
     szs_buffer_release(&engine->device_outputs);
     szs_buffer_release(&engine->device_search_hashes);
-    szs_buffer_release(&engine->device_search_scratch);
-    szs_buffer_release(&engine->device_search_lists);
-    szs_buffer_release(&engine->device_search_out);
+    szs_selection_release(&engine->selection);
     engine->parameters_device = -1;
 }
 

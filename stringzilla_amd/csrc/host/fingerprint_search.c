@@ -5,17 +5,13 @@
  *
  *  Both calls are cut into blocks of queries x tiles of candidates.  hip/fingerprint_matches.hip counts a tile; the matrix call
  *  writes it where the caller wants it, the search writes 8-byte cells into a device scratch matrix that hip/top_k.hip folds into
- *  each query's running list - the very selection the similarity engines use (host/top_k.c), descending.  Hash matrices the device
+ *  each query's running list - the very selection the similarity engines use (host/selection.c), descending.  Hash matrices the device
  *  cannot read (plain host memory) are staged: the query block once per block, the candidate rows once per tile, so a corpus of
  *  any size passes through a bounded device buffer.  Everything runs on the scope's stream; both calls are synchronous.
  */
-#include "szs_internal.h"
+#include "selection_internal.h"
 
-#define SZS_SEARCH_SCRATCH_CELLS ((size_t)16 << 20) /* as host/top_k.c: a tile the fold re-reads from the Infinity Cache */
-#define SZS_SEARCH_LIST_BYTES ((size_t)128 << 20)   /* running lists of one block of queries */
-#define SZS_SEARCH_MOST_ROWS ((size_t)1 << 18)      /* per side of a tile */
-#define SZS_SEARCH_WORKGROUPS 2048u                 /* the scan wants ~8 workgroups per CU: rows are split into segments below that */
-#define SZS_SEARCH_STAGE_BYTES ((size_t)256 << 20)  /* per side: hashes staged from memory the device cannot read */
+#define SZS_SEARCH_STAGE_BYTES ((size_t)256 << 20) /* per side: hashes staged from memory the device cannot read */
 
 static size_t at_most(size_t value, size_t limit) { return value < limit ? value : limit; }
 static size_t at_least_one(size_t value) { return value ? value : 1; }
@@ -103,11 +99,11 @@ sz_status_t szs_fingerprints_matches(szs_fingerprints_s *engine, szs_scope_s *sc
     if (!pool.device_accessible) tile = at_most(tile, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
     if (!direct) {
         block = at_most(block, 4096);
-        tile = at_most(tile, 2 * SZS_SEARCH_SCRATCH_CELLS / block);
+        tile = at_most(tile, 2 * SZS_SELECTION_SCRATCH_CELLS / block);
     }
     status = reserve_staging(engine, device, &queries, block, &pool, tile, row_bytes, error_message);
     if (status == sz_success_k && !direct)
-        status = szs_buffer_reserve(&engine->device_search_scratch, szs_memory_device_k, device, block * tile * sizeof(uint32_t), error_message);
+        status = szs_buffer_reserve(&engine->selection.scratch, szs_memory_device_k, device, block * tile * sizeof(uint32_t), error_message);
     if (status != sz_success_k) return status;
 
     hipError_t error = hipSuccess;
@@ -120,7 +116,7 @@ sz_status_t szs_fingerprints_matches(szs_fingerprints_s *engine, szs_scope_s *sc
             size_t const columns = at_most(c_count - c0, tile);
             error = side_rows(&pool, c0, columns, row_bytes, stream, &pool_rows, &pool_stride);
             if (error != hipSuccess) break;
-            uint32_t *const target = direct ? (uint32_t *)((char *)counts + q0 * counts_stride) + c0 : (uint32_t *)engine->device_search_scratch.pointer;
+            uint32_t *const target = direct ? (uint32_t *)((char *)counts + q0 * counts_stride) + c0 : (uint32_t *)engine->selection.scratch.pointer;
             size_t const target_stride = direct ? counts_stride : columns * sizeof(uint32_t);
             error = (hipError_t)szs_hip_fingerprint_matches_u32(query_rows, query_stride, (uint32_t)rows, pool_rows, pool_stride, (uint32_t)columns,
                                                                 dimensions, target, target_stride, stream);
@@ -163,38 +159,17 @@ sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scop
         pool.rows = (char const *)candidate_hashes, pool.stride = candidate_hashes_stride, pool.count = c_count;
         pool.device_accessible = szs_classify_pointer(candidate_hashes).device_accessible;
     }
-    size_t const width = szs_hip_top_k_width((uint32_t)k), list_bytes = 2 * width * sizeof(uint64_t);
 
-    /* the budget of host/top_k.c - blocks of queries whose lists fit, tiles of candidates whose counts fit the scratch matrix, row
-     * segments so that the scan fills the GPU - and on top of it the staging areas of hashes the device cannot read */
-    size_t block = at_most(q_count, SZS_SEARCH_MOST_ROWS);
-    block = at_most(block, SZS_SEARCH_LIST_BYTES / list_bytes);
-    size_t const wide = c_count < 4096 ? at_least_one(c_count) : 4096;
-    block = at_most(block, SZS_SEARCH_SCRATCH_CELLS / wide);
-    if (!queries.device_accessible) block = at_most(block, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
-    size_t tile = at_most(SZS_SEARCH_SCRATCH_CELLS / block, SZS_SEARCH_MOST_ROWS);
-    if (!pool.device_accessible) tile = at_most(tile, at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes));
-    int const knob = szs_tuning_get(szs_knob_top_k_tile_k);
-    if (knob > 0 && (size_t)knob < tile) tile = (size_t)knob;
-    if (tile > c_count) tile = at_least_one(c_count);
-    size_t segments = (SZS_SEARCH_WORKGROUPS + block - 1) / block;
-    if (segments > tile / 4096) segments = tile / 4096;
-    if (segments < 1) segments = 1;
-    size_t const partial_bytes = segments > 1 ? block * segments * list_bytes : 0;
-
+    /* the shared budget, within the staging areas of hashes the device cannot read */
+    size_t const most_staged = at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes);
+    szs_selection_t selection = {.stream = stream, .device = device, .k = k, .row_stride = row_stride, .descending = 1 /* most matches first */,
+                                 .indices = (uint64_t *)indices, .scores = (uint64_t *)matches,
+                                 .plan = szs_selection_plan(q_count, c_count, k, queries.device_accessible ? SIZE_MAX : most_staged,
+                                                            pool.device_accessible ? SIZE_MAX : most_staged)};
+    size_t const block = selection.plan.block, tile = selection.plan.tile;
     status = reserve_staging(engine, device, &queries, block, &pool, tile, row_bytes, error_message);
-    if (status == sz_success_k)
-        status = szs_buffer_reserve(&engine->device_search_scratch, szs_memory_device_k, device, block * tile * sizeof(uint64_t), error_message);
-    if (status == sz_success_k)
-        status = szs_buffer_reserve(&engine->device_search_lists, szs_memory_device_k, device, block * list_bytes + partial_bytes, error_message);
-    /* outputs a kernel can write go straight there; others (plain host memory) are staged densely and copied in one piece */
-    int const direct = szs_classify_pointer(indices).device_accessible && (!matches || szs_classify_pointer(matches).device_accessible);
-    if (status == sz_success_k && !direct)
-        status = szs_buffer_reserve(&engine->device_search_out, szs_memory_device_k, device, 2 * block * k * sizeof(uint64_t), error_message);
+    if (status == sz_success_k) status = szs_selection_reserve(&selection, &engine->selection, error_message);
     if (status != sz_success_k) return status;
-    uint64_t *const lists = (uint64_t *)engine->device_search_lists.pointer;
-    uint64_t *const partials = lists + block * 2 * width;
-    uint64_t *const cells = (uint64_t *)engine->device_search_scratch.pointer;
 
     hipError_t error = hipSuccess;
     for (size_t q0 = 0; q0 < q_count && error == hipSuccess; q0 += block) {
@@ -202,34 +177,18 @@ sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scop
         uint32_t const *query_rows = NULL, *pool_rows = NULL;
         uint64_t query_stride = 0, pool_stride = 0;
         error = side_rows(&queries, q0, rows, row_bytes, stream, &query_rows, &query_stride);
-        if (error == hipSuccess) error = hipMemsetAsync(lists, 0xFF, rows * list_bytes, stream); /* empty lists */
+        if (error == hipSuccess) error = szs_selection_block_begin(&selection, rows);
         for (size_t c0 = 0; c0 < c_count && error == hipSuccess; c0 += tile) {
             size_t const columns = at_most(c_count - c0, tile);
             error = side_rows(&pool, c0, columns, row_bytes, stream, &pool_rows, &pool_stride);
             if (error == hipSuccess)
                 error = (hipError_t)szs_hip_fingerprint_matches_u64(query_rows, query_stride, (uint32_t)rows, pool_rows, pool_stride,
-                                                                    (uint32_t)columns, dimensions, cells, columns, stream);
-            if (error == hipSuccess)
-                error = (hipError_t)szs_hip_top_k_scan(cells, columns, (uint32_t)rows, (uint32_t)columns, c0, self ? q0 : ~(uint64_t)0, lists,
-                                                       partials, (uint32_t)segments, (uint32_t)k, 1 /* most matches first */, stream);
+                                                                    (uint32_t)columns, dimensions, selection.cells, columns, stream);
+            if (error == hipSuccess) error = szs_selection_fold(&selection, q0, rows, c0, columns, self);
         }
-        if (error != hipSuccess) break;
-        if (direct)
-            error = (hipError_t)szs_hip_top_k_emit(lists, (uint32_t)rows, (uint32_t)k, (uint64_t *)indices + q0 * row_stride,
-                                                   matches ? (uint64_t *)matches + q0 * row_stride : NULL, row_stride, 1, stream);
-        else {
-            uint64_t *const staged_indices = (uint64_t *)engine->device_search_out.pointer, *const staged_matches = staged_indices + rows * k;
-            error = (hipError_t)szs_hip_top_k_emit(lists, (uint32_t)rows, (uint32_t)k, staged_indices, staged_matches, k, 1, stream);
-            if (error == hipSuccess)
-                error = hipMemcpy2DAsync((uint64_t *)indices + q0 * row_stride, row_stride * sizeof(uint64_t), staged_indices,
-                                         k * sizeof(uint64_t), k * sizeof(uint64_t), rows, hipMemcpyDefault, stream);
-            if (error == hipSuccess && matches)
-                error = hipMemcpy2DAsync((uint64_t *)matches + q0 * row_stride, row_stride * sizeof(uint64_t), staged_matches,
-                                         k * sizeof(uint64_t), k * sizeof(uint64_t), rows, hipMemcpyDefault, stream);
-        }
+        if (error == hipSuccess) error = szs_selection_emit(&selection, q0, rows);
     }
-    hipError_t const drained = hipStreamSynchronize(stream); /* synchronous, also when it fails */
-    if (error == hipSuccess) error = drained;
+    error = szs_selection_drain(&selection, error);
     if (error != hipSuccess) return szs_report_hip(error, error_message);
     return szs_report(sz_success_k, error_message, NULL);
 }

@@ -33,18 +33,11 @@
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #define SZS_NODE_MAGIC 0x535A4E44u
 #define SZS_NODE_ENGINE_MAGIC 0x535A4E45u
 
 void szs_engine_release(szs_engine_s *engine); /* dispatch.c */
-
-static double node_now_milliseconds(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
 
 typedef struct szs_node_s {
     uint32_t magic;
@@ -346,7 +339,7 @@ static void *node_worker(void *argument) {
     szs_node_engine_s *engine = task->engine;
     szs_node_s *node = engine->node;
     size_t const shard = task->shard;
-    double const started = node_now_milliseconds();
+    double const started = szs_now_milliseconds();
     task->status = sz_success_k, task->message = NULL;
     if (!task->rows_count) return NULL;
 
@@ -361,7 +354,7 @@ static void *node_worker(void *argument) {
     if (task->symmetric) { /* one tape plays both roles: see node_band */
         if (task->status == sz_success_k) node_band(task, device, stream, query_base);
         else (void)hipStreamSynchronize(stream);
-        task->busy_milliseconds = node_now_milliseconds() - started;
+        task->busy_milliseconds = szs_now_milliseconds() - started;
         return NULL;
     }
     if (task->status == sz_success_k)
@@ -407,7 +400,7 @@ static void *node_worker(void *argument) {
     hipError_t const drained = hipStreamSynchronize(stream);
     if (error == hipSuccess) error = drained;
     if (error != hipSuccess) task->status = szs_report_hip(error, &task->message);
-    task->busy_milliseconds = node_now_milliseconds() - started;
+    task->busy_milliseconds = szs_now_milliseconds() - started;
     return NULL;
 }
 
@@ -463,7 +456,7 @@ static sz_status_t node_cross(szs_node_engine_s *engine, int wide, int symmetric
                               size_t queries_count, char const *candidate_data, void const *candidate_offsets_raw, size_t candidates_count,
                               void *results, size_t results_row_stride, szs_rocm_node_stats_t *stats, char const **error_message) {
     if (!engine || engine->magic != SZS_NODE_ENGINE_MAGIC) return szs_report(sz_status_unknown_k, error_message, "Engine must be initialized");
-    double const started = node_now_milliseconds();
+    double const started = szs_now_milliseconds();
     szs_node_s *node = engine->node;
     if (stats) memset(stats, 0, sizeof(*stats)), stats->gpus = node->count, stats->peer_pairs = node->peer_pairs, stats->symmetric = symmetric != 0;
     if (!queries_count || !candidates_count) return szs_report(sz_success_k, error_message, NULL);
@@ -552,7 +545,7 @@ static sz_status_t node_cross(szs_node_engine_s *engine, int wide, int symmetric
         }
         /* every band has landed: the cells above the diagonal that belong to other bands' rows */
         if (status == sz_success_k && shards > 1) status = node_mirror(node, results, queries_count, results_row_stride, error_message);
-        if (stats) stats->wall_milliseconds = node_now_milliseconds() - started;
+        if (stats) stats->wall_milliseconds = szs_now_milliseconds() - started;
         if (status == sz_success_k && error_message) *error_message = NULL;
         return status;
     }
@@ -614,7 +607,7 @@ static sz_status_t node_cross(szs_node_engine_s *engine, int wide, int symmetric
             stats->peer_copies[s] = tasks[s].peer_copies, stats->staged_copies[s] = tasks[s].staged_copies;
         }
     }
-    if (stats) stats->wall_milliseconds = node_now_milliseconds() - started;
+    if (stats) stats->wall_milliseconds = szs_now_milliseconds() - started;
     if (status == sz_success_k && error_message) *error_message = NULL;
     return status;
 }

@@ -1,7 +1,8 @@
 /*
  *  rerank_internal.h - what the calls over LISTED pairs share on the host (rerank.c: szs_rocm_rerank*; fuzzy_find.c:
- *  szs_rocm_fuzzy_find*; fuzzy_search.c: szs_rocm_fuzzy_search*, for its strings and its winners): the block and staging budgets, the deal of a block's rows by descending query length, and the skeleton of
- *  such a call (listed_pairs.c): its preamble, the validation of indices, the scratch, the two sides as the kernels read them, and
+ *  szs_rocm_fuzzy_find*; fuzzy_search.c: szs_rocm_fuzzy_search*, for its strings and its winners - its tiles and lists are
+ *  selection_internal.h's): the block and staging budgets, the deal of a block's rows by descending query length, and the skeleton
+ *  of such a call (listed_pairs.c): its preamble, the validation of indices, the scratch, the two sides as the kernels read them, and
  *  the bracket around a block's launches.  Policy stays with the callers: which engines, which lengths, what an unusable side means.
  */
 #ifndef SZS_RERANK_INTERNAL_H_
@@ -10,17 +11,10 @@
 #include "szs_internal.h"
 
 #include <string.h>
-#include <time.h>
 
 #define SZS_RERANK_STAGE_BYTES ((size_t)128 << 20) /* a block's dense copy of an array the device cannot reach */
 #define SZS_RERANK_MOST_ROWS ((size_t)1 << 20)     /* rows of a block: bounds the kernel's row list */
 #define SZS_RERANK_EMPTY (~(uint64_t)0)            /* SZ_SIZE_MAX: the empty slot top-k emits */
-
-static inline double szs_now_milliseconds(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
 
 static inline uint64_t szs_tape_offset(szs_input_t const *input, void const *offsets, size_t i) {
     return input->kind == szs_input_u32tape_k ? ((uint32_t const *)offsets)[i] : ((uint64_t const *)offsets)[i];

@@ -1,5 +1,5 @@
 /*
- *  runtime.c - version, capabilities, unified allocator, device scopes, status strings, grow-only buffers.
+ *  runtime.c - version, capabilities, unified allocator, device scopes, status strings, the clock, grow-only buffers.
  *
  *  ROCm counterpart of the reference's c/stringzillas/runtime.cuh (226 lines) and of the error plumbing in
  *  c/stringzillas/stringzillas.cuh:207-257.  Same entry points, same status conventions; HIP instead of the
@@ -9,6 +9,7 @@
 
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 /* ---- status strings ---------------------------------------------------------------------------------------------- */
 
@@ -43,6 +44,12 @@ sz_status_t szs_report_hip(hipError_t error, char const **error_message) {
                                                               : sz_status_unknown_k;
     (void)hipGetLastError(); /* clear the sticky error so the next call starts clean */
     return szs_report(status, error_message, hipGetErrorName(error));
+}
+
+double szs_now_milliseconds(void) {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
 /* ---- version & capabilities (runtime.cuh:15-56) ------------------------------------------------------------------ */

@@ -60,6 +60,17 @@ sz_status_t szs_buffer_reserve(szs_buffer_t *buffer, szs_memory_kind_t kind, int
                                char const **error_message);
 void szs_buffer_release(szs_buffer_t *buffer);
 
+/** The device buffers of a tiled selection (selection_internal.h): grow-only, released with the engine that holds them. */
+typedef struct szs_selection_buffers_t {
+    szs_buffer_t scratch; /* the scored tile */
+    szs_buffer_t lists;   /* running lists of a block of queries, then the segments' partial lists */
+    szs_buffer_t out;     /* emitted rows of a block when the caller's arrays are not device-accessible */
+} szs_selection_buffers_t;
+void szs_selection_release(szs_selection_buffers_t *buffers);
+
+/** The monotonic clock, for the host times of the call profiles (runtime.c). */
+double szs_now_milliseconds(void);
+
 /* ---- engines ----------------------------------------------------------------------------------------------------- */
 
 typedef enum {
@@ -151,13 +162,11 @@ typedef struct szs_engine_s {
     uint32_t plan_sequence;        /* echoed by the planner: tells this call's summary from a stale one */
     struct szs_decision_t *remembered; /* the launch shape of the previous device-planned call (speculation), or NULL */
 
-    /* top-k calls (host/top_k.c) */
-    szs_buffer_t device_top_k_scratch; /* device: the scored tile */
-    szs_buffer_t device_top_k_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
-    szs_buffer_t device_top_k_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
+    /* top-k calls (host/top_k.c) and fuzzy searches (host/fuzzy_search.c) */
+    szs_selection_buffers_t selection;
 
     /* rerank calls (host/rerank.c); fuzzy-find calls (host/fuzzy_find.c) lay their own parts out in the same buffers, and so does a
-     * fuzzy search (host/fuzzy_search.c), which scores into the top-k buffers above */
+     * fuzzy search (host/fuzzy_search.c), which scores into the selection buffers above */
     szs_buffer_t host_rerank_offsets[2]; /* host: tape offsets only the device can read - queries, candidates */
     szs_buffer_t host_rerank;            /* host: query lengths, gathered strings, a block of indices only the device can read, a row's picks */
     szs_buffer_t pinned_rerank;          /* pinned: the kernel's flag, its counters, a row's cells and image, the kernel's rows, refs of both sides */
@@ -223,9 +232,7 @@ struct szs_fingerprints_s {
 
     /* fingerprint search (host/fingerprint_search.c): buffers of their own, so a search never disturbs a hashing call */
     szs_buffer_t device_search_hashes;  /* device: the query block, then the candidate tile, of hashes that live in plain host memory */
-    szs_buffer_t device_search_scratch; /* device: the tile of match counts (8-byte cells: top-k; 4-byte cells: a staged matrix) */
-    szs_buffer_t device_search_lists;   /* device: running lists of a block of queries, then the segments' partial lists */
-    szs_buffer_t device_search_out;     /* device: emitted rows of a block when the caller's arrays are not device-accessible */
+    szs_selection_buffers_t selection;  /* device: top-k's; the matrix call stages 4-byte counts in its scratch */
 };
 
 sz_status_t szs_fingerprints_create(sz_size_t dimensions, sz_size_t alphabet_size, sz_size_t const *window_widths,

@@ -316,6 +316,23 @@ def test_top_k_automatic_tiling_segments_and_tiles(gpu):
         assert np.array_equal(from_device[0], from_host[0]) and np.array_equal(from_device[1], from_host[1]), rows
 
 
+def test_top_k_self_search_in_two_blocks_of_queries(gpu):
+    """4,200 fingerprints against themselves: with 4,096 or more candidates a block is 16 M cells / 4096 = 4,096 queries, so a second
+    block of 104 begins at query 4,096 - the row that both its self-exclusion and its rows of the host outputs (staged) start from."""
+    rng = np.random.default_rng(31)
+    engine = _engine(1, gpu)
+    a = _draw(rng, 4200, 1)  # one dimension of four values: every count is 0 or 1, a quarter of each row ties at the top
+    a[4100], a[4150], a[10], a[4199] = 7, 7, 9, 9  # twins no other row equals: without its own column each finds the other first
+    want = expected_top_k(expected_matches(a, a), 5, self_search=True)
+    wide_indices = np.full((4200, 6), UNTOUCHED, dtype=np.uint64)
+    wide_matches = np.full((4200, 6), UNTOUCHED, dtype=np.uint64)
+    engine.top_k(a, None, k=5, device=gpu, out=(wide_indices[:, :5], wide_matches[:, :5]))
+    assert np.array_equal(wide_indices[:, :5], want[0]) and np.array_equal(wide_matches[:, :5], want[1])
+    assert (wide_indices[:, 5] == UNTOUCHED).all() and (wide_matches[:, 5] == UNTOUCHED).all()
+    assert not (wide_indices[:, :5] == np.arange(4200, dtype=np.uint64)[:, None]).any()  # never the own index, in either block
+    assert wide_indices[[4100, 4150, 10, 4199], :2].tolist() == [[4150, 0], [4100, 0], [4199, 0], [10, 0]]
+
+
 def test_other_handles_are_refused_on_the_gpu(gpu):
     similarity = szs.LevenshteinDistances(capabilities=gpu)
     a = _draw(np.random.default_rng(4), 2, 64)

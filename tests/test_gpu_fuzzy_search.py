@@ -164,6 +164,23 @@ def test_tiles_and_segments(gpu, engine, knobs, widths_ab, tile):
         assert same(engine.fuzzy_search(queries, candidates, k=k, device=gpu), without_starts(select(want, k)))
 
 
+def test_scan_segments_share_a_row(gpu, engine, knobs):
+    """3 x 8,200 at the automatic sizes: one tile whose rows the scan splits into two segments (8200 // 4096), at column 5,120.  Strings
+    over two letters: every row's ties at the best distance run across that boundary, and the merge of the segments' lists must still
+    give them to the lower index."""
+    rng = random.Random(77)
+    queries = [bytes(rng.choice(b"ab") for _ in range(length)) for length in (1, 4, 6)]
+    candidates = [bytes(rng.choice(b"ab") for _ in range(rng.randint(0, 10))) for _ in range(8200)]
+    block, tile, _, _ = _abi.fuzzy_search_probe(len(queries), len(candidates), 16)
+    assert (block, tile) == (3, 8200)  # one tile of at least 2 x 4096 columns, few rows: the scan takes segments
+    cells = dense(queries, candidates)
+    assert all((row[:5120] == row.min()).sum() > 16 and (row[5120:] == row.min()).sum() > 16 for row in cells[0])  # full lists of ties on both sides
+    want = select(cells, 16)
+    got = engine.fuzzy_search(queries, candidates, k=16, device=gpu, starts=True)
+    for name, g, w in zip(("indices", "distances", "starts", "ends"), got, want):
+        assert np.array_equal(g, w), (name, np.argwhere(g != w)[:8])
+
+
 def test_ties_and_empty_slots(gpu, engine):
     rng = random.Random(12)
     text = bytes(rng.choice(b"ACGT") for _ in range(90))
