@@ -23,6 +23,8 @@
  *  - szs_rocm_fuzzy_find_spans* : the same call with the whole span: where that best match starts as well.
  *  - szs_rocm_fuzzy_search*     : the k candidates of a corpus that contain the best such match per query, without the matrix
  *    (csrc/host/fuzzy_search.c); szs_rocm_fuzzy_search_probe reports how a call would be cut.
+ *  - szs_rocm_fuzzy_scan*       : the best match of every query inside ONE long text, the text cut over the device's lanes
+ *    (csrc/host/fuzzy_scan.c); szs_rocm_fuzzy_scan_spans* add the starts, szs_rocm_fuzzy_scan_probe reports the cut.
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -294,6 +296,75 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_probe(sz_size_t queries_count, 
                                                        sz_size_t *workgroups);
 
 /**
+ *  Fuzzy SCAN: many short patterns in ONE long text - a chromosome, a book, a log file, a concatenated corpus.  For every query q
+ *  of m bytes and the text c of n = `text_length` bytes, with D szs_rocm_fuzzy_find's unit-cost DP with a free start in the text:
+ *      distances[q] = min over j in [0, n] of D[m][j];
+ *      ends[q]      = the smallest j that attains it;
+ *      starts[q]    = szs_rocm_fuzzy_find_spans' start for that pair (szs_rocm_fuzzy_scan_spans*).
+ *  These are exactly the values szs_rocm_fuzzy_find(queries, [text]) / szs_rocm_fuzzy_find_spans return in column 0, bit for bit -
+ *  but that call walks the whole text on one lane per query, a serial chain of n columns, and this one fills the device.  The
+ *  outputs are vectors of `queries.count` 8-byte cells, no row stride.  `ends` may be NULL; the spans twins require all three.
+ *  A query of no bytes gives (0, 0, 0); an empty text gives (m, 0, 0).
+ *
+ *  HOW, and why it is exact (csrc/hip/myers_fuzzy_scan.hip, csrc/host/fuzzy_scan.c).  The text is cut into
+ *  pieces of P bytes; piece p owns columns (p P, min(n, (p + 1) P)].  The lane that takes it walks from s = max(0, p P - 2 m) - a
+ *  warm-up of min(p P, 2 m) bytes ahead of its own - follows (best, leftmost end) over every column it walks and reports
+ *  (best, s + end); the answer is the lexicographic minimum of (distance, end) over the pieces, by one 64-bit atomic minimum per
+ *  (query, 64 pieces).  (1) A DP that starts at s chooses among fewer starts: every value it sees is >= the true D[m][j], no piece
+ *  reports too little.  (2) For j - s >= 2 m, or s = 0, the value is exact: the start that attains D[m][j] lies within
+ *  m + D[m][j] <= 2 m bytes of j - so the piece that owns the true leftmost best end j* reports exactly (d, j*).  (3) Any other
+ *  piece that reports d at a column e has d >= D[m][e] >= d: e is a true best end too, and e >= j*.  Where nothing occurs piece 0
+ *  reports (m, 0) and every other piece (m, s > 0).  The starts are szs_rocm_fuzzy_find_spans' reverse pass, unchanged, over at most
+ *  m + distance bytes back from `end`.
+ *
+ *  LIMITS.  (1) `engine` must be a unit-cost BYTE Levenshtein engine, as for szs_rocm_fuzzy_find.  (2) Every query has at most 256
+ *  bytes.  (3) The text has less than 4 GiB: the kernels' lengths and ends are 32-bit, as candidates' are.  (4) The text must be
+ *  readable by the device (device, pinned or unified memory); the queries likewise.  The outputs may live in device, pinned, unified
+ *  or plain host memory (staged densely and copied home).
+ *
+ *  Refusals, in this order, before any launch and with nothing written: `text_length` >= 2^32 - sz_unexpected_dimensions_k; an engine
+ *  that is NULL, blank or not unit-cost byte Levenshtein - sz_status_unknown_k; NULL `queries` - sz_status_unknown_k; zero queries -
+ *  success, nothing is looked at; a NULL `distances`, or (the spans twins) a NULL `starts` or `ends` - sz_status_unknown_k; a NULL
+ *  `text` with `text_length` > 0, or a text the device cannot read - sz_status_unknown_k; a query of more than 256 bytes -
+ *  sz_unexpected_dimensions_k.  Synchronous, also when it fails.
+ *
+ *  Blocks of at most 2^20 queries; per block the scan, its emit and - with starts - the reverse pass, on the scope's stream.  The
+ *  piece: P = ceil(n / (64 x ceil(20480 / rows))), rounded up to a multiple of 64 and at least 4096 - enough wavefronts to fill the
+ *  device four times over, and the warm-up of the longest query at most an eighth of a lane's walk.  The `fuzzy_scan_piece` knob
+ *  sets P (rounded up to a multiple of 64); like every knob it changes no result.  szs_rocm_last_call_profile: pairs = the queries
+ *  of at least one byte (none for an empty text), cells = m x the bytes walked, warm-ups included, plus the reverse windows',
+ *  launches = 2 per block (3 with starts; the scan is not launched for an empty text), kernel time = the event pair around them.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, void const *text,
+                                               sz_size_t text_length, sz_size_t *distances, sz_size_t *ends, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                       void const *text, sz_size_t text_length, sz_size_t *distances, sz_size_t *ends,
+                                                       char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                       void const *text, sz_size_t text_length, sz_size_t *distances, sz_size_t *ends,
+                                                       char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_spans(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, void const *text,
+                                                     sz_size_t text_length, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                     char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_spans_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                             void const *text, sz_size_t text_length, sz_size_t *distances,
+                                                             sz_size_t *starts, sz_size_t *ends, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_spans_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                             void const *text, sz_size_t text_length, sz_size_t *distances,
+                                                             sz_size_t *starts, sz_size_t *ends, char const **error_message);
+
+/**
+ *  How szs_rocm_fuzzy_scan would cut a text of `text_length` bytes for `queries_count` queries - host only, no GPU: the bytes of a
+ *  piece (a multiple of 64), the pieces, the workgroups of the first block's scan = its rows x ceil(pieces / 64), and the bytes a
+ *  query of `longest_query` bytes walks: text_length + the sum over the pieces p of min(p x piece, 2 x longest_query).  The
+ *  `fuzzy_scan_piece` knob applies as it does to the call.  Outputs are optional.  `longest_query` above 256 or `text_length` >= 2^32:
+ *  sz_unexpected_dimensions_k.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_probe(sz_size_t queries_count, sz_size_t longest_query, sz_size_t text_length,
+                                                     sz_size_t *piece, sz_size_t *pieces, sz_size_t *workgroups,
+                                                     sz_size_t *walked_bytes_per_query);
+
+/**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine
  *  - it supplies `dimensions` and owns the device scratch; any other handle is refused and nothing is written.  Hash matrices are
  *  row-major `sz_u32_t` with a row stride in BYTES, a multiple of 4 and at least 4 * dimensions, exactly as `szs_fingerprints_*`
@@ -493,6 +564,8 @@ SZ_API_RUNTIME sz_status_t szs_rocm_node_scores_u64tape(szs_rocm_node_engine_t e
  *  hip/myers_rerank_strips.hip),
  *  "fuzzy_search_segment" (n: the candidates one workgroup of hip/myers_fuzzy_tile.hip scores for its row in a fuzzy search, rounded
  *  up to a multiple of 64; automatic: enough workgroups to fill the device four times over),
+ *  "fuzzy_scan_piece" (n: the bytes of the text one lane of hip/myers_fuzzy_scan.hip owns in a fuzzy scan, rounded up to a multiple
+ *  of 64; automatic: enough wavefronts to fill the device four times over, at least 4096 bytes),
  *  "queues" (see below), "roctx" (1: the host phases of every call - plan, decide, enqueue, wait - as roctx ranges for a
  *  `rocprofv3 --marker-trace` timeline; the marker library is looked up at run time, never linked),
  *  "cpu_requests" (strict | gpu: serve capability

@@ -538,6 +538,74 @@ class _Engine:
             return out
         return tuple(matrix.view(np.uint64) for matrix in results[:, :rows].cpu().numpy())
 
+    def fuzzy_scan(self, queries, text, device: Optional[DeviceScope] = None, out=None, starts=False):
+        """The best match of every query inside ONE long text (`szs_rocm_fuzzy_scan_*`): returns `(distances, ends)`, two `uint64`
+        NumPy vectors of `len(queries)` - exactly column 0 of `fuzzy_find(queries, [text])`, with the text cut over the device's lanes
+        instead of walked on one.  `text` is bytes-like, a NumPy `uint8` array or a torch `uint8` tensor: a tensor on the call's GPU
+        goes as a raw pointer, host data is uploaded once.  `starts=True` (`szs_rocm_fuzzy_scan_spans_*`): returns
+        `(distances, starts, ends)` - `text[starts[q]:ends[q]]` is the shortest best match that ends at `ends[q]`.  `out`: a pair -
+        with `starts` a triple - of contiguous NumPy vectors or torch tensors of `len(queries)` 8-byte cells in that order, filled
+        and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes, a text below 4 GiB."""
+        import torch
+
+        names = ("out distances", "out starts", "out ends") if starts else ("out distances", "out ends")
+        queries = _as_strs(queries)
+        rows = len(queries)
+        is_tensor = type(text).__module__.partition(".")[0] == "torch" and hasattr(text, "data_ptr")
+        if is_tensor:
+            if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+                raise ValueError("`text` must be a contiguous vector of uint8")
+        elif isinstance(text, np.ndarray):
+            if text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
+                raise ValueError("`text` must be a contiguous vector of uint8")
+        elif isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        else:
+            raise ValueError(f"`text` must be bytes-like, a NumPy uint8 array or a torch uint8 tensor, got {type(text).__name__}")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != len(names):
+                raise ValueError("`out` must be a triple (distances, starts, ends)" if starts else "`out` must be a pair (distances, ends)")
+            pointers = []
+            for vector, name in zip(out, names):
+                if isinstance(vector, np.ndarray):
+                    shape, itemsize, unit, pointer = vector.shape, vector.dtype.itemsize, vector.strides == (8,), vector.ctypes.data
+                elif type(vector).__module__.partition(".")[0] == "torch" and hasattr(vector, "data_ptr"):
+                    shape, itemsize, unit, pointer = tuple(vector.shape), vector.element_size(), vector.stride() == (1,), vector.data_ptr()
+                else:
+                    raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(vector).__name__}")
+                if shape != (rows,) or itemsize != 8 or (rows > 1 and not unit):
+                    raise ValueError(f"`{name}` must be a contiguous vector of {rows} 8-byte cells")
+                pointers.append(pointer)
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        for vector, name in ((text, "text"),) + (tuple(zip(out, names)) if out is not None else ()):
+            if getattr(vector, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
+                if vector.device.index != gpu_device:
+                    raise ValueError(f"`{name}` is on {vector.device}, the call runs on GPU {gpu_device}")
+                torch.cuda.current_stream(vector.device).synchronize()  # torch's own stream may still be filling it
+        where = torch.device("cuda", gpu_device)
+        if not is_tensor:
+            text = torch.from_numpy(np.array(text, copy=True) if not text.flags.writeable else text)
+        if not text.is_cuda:  # host data: uploaded once
+            text = text.to(where)
+            torch.cuda.current_stream(where).synchronize()
+        if out is None:
+            results = torch.empty((len(names), max(rows, 1)), dtype=torch.int64, device=where)
+            pointers = [vector.data_ptr() for vector in results]
+
+        error = ctypes.c_char_p()
+        if starts:
+            call = lib.szs_rocm_fuzzy_scan_spans_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_scan_spans_u32tape
+        else:
+            call = lib.szs_rocm_fuzzy_scan_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_scan_u32tape
+        q_tape = queries._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), text.data_ptr() if text.numel() else None, text.numel(), *pointers,
+                      ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        return tuple(vector.view(np.uint64) for vector in results[:, :rows].cpu().numpy())
+
     def __del__(self):
         handle = getattr(self, "handle", None)
         if handle and self._free is not None:

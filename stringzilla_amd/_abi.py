@@ -86,6 +86,8 @@ _RERANK = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c
 _FUZZY_FIND = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ERR])
 _FUZZY_FIND_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 _FUZZY_SEARCH = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
+_FUZZY_SCAN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ERR])
+_FUZZY_SCAN_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
 
 SIGNATURES = {
     "szs_version_major": (c_int, []), "szs_version_minor": (c_int, []), "szs_version_patch": (c_int, []),
@@ -144,6 +146,11 @@ SIGNATURES = {
     "szs_rocm_fuzzy_search": _FUZZY_SEARCH, "szs_rocm_fuzzy_search_u32tape": _FUZZY_SEARCH, "szs_rocm_fuzzy_search_u64tape": _FUZZY_SEARCH,
     "szs_rocm_fuzzy_search_probe": (c_int, [c_size_t, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
                                             ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "szs_rocm_fuzzy_scan": _FUZZY_SCAN, "szs_rocm_fuzzy_scan_u32tape": _FUZZY_SCAN, "szs_rocm_fuzzy_scan_u64tape": _FUZZY_SCAN,
+    "szs_rocm_fuzzy_scan_spans": _FUZZY_SCAN_SPANS, "szs_rocm_fuzzy_scan_spans_u32tape": _FUZZY_SCAN_SPANS,
+    "szs_rocm_fuzzy_scan_spans_u64tape": _FUZZY_SCAN_SPANS,
+    "szs_rocm_fuzzy_scan_probe": (c_int, [c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                          ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "szs_rocm_rerank_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "szs_rocm_fingerprint_matches": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t,
                                              c_void_p, c_size_t, ERR]),
@@ -191,7 +198,7 @@ _KNOBS = {"tier": "SZS_ROCM_TIER", "swap": "SZS_ROCM_SWAP", "packed": "SZS_ROCM_
           "queue": "SZS_ROCM_QUEUE", "queue_words": "SZS_ROCM_QUEUE_WORDS", "queue_rounds": "SZS_ROCM_QUEUE_ROUNDS",
           "queue_priority": "SZS_ROCM_QUEUE_PRIORITY", "fused": "SZS_ROCM_FUSED", "tiny": "SZS_ROCM_TINY",
           "top_k_tile": "SZS_ROCM_TOP_K_TILE", "rerank": "SZS_ROCM_RERANK",
-          "fuzzy_search_segment": "SZS_ROCM_FUZZY_SEARCH_SEGMENT"}
+          "fuzzy_search_segment": "SZS_ROCM_FUZZY_SEARCH_SEGMENT", "fuzzy_scan_piece": "SZS_ROCM_FUZZY_SCAN_PIECE"}
 _knob_values = {name: os.environ.get(variable) for name, variable in _KNOBS.items()}  # what the library read when it was loaded
 
 
@@ -233,6 +240,19 @@ def fuzzy_search_probe(queries_count, candidates_count, k, longest_query=0):
     if status != 0:
         raise StringZillasError(status, None)
     return int(block.value), int(tile.value), int(segment.value), int(workgroups.value)
+
+
+def fuzzy_scan_probe(queries_count, longest_query, text_length):
+    """`szs_rocm_fuzzy_scan_probe`: how a fuzzy scan would cut a text of `text_length` bytes for `queries_count` queries - no GPU
+    involved.  Returns (piece, pieces, workgroups, walked_bytes_per_query): the bytes of a piece, the pieces, the workgroups of the
+    first block's scan and the bytes a query of `longest_query` bytes walks, warm-ups included.  The `fuzzy_scan_piece` knob applies
+    as it does to the call."""
+    piece, pieces, workgroups, walked = c_size_t(0), c_size_t(0), c_size_t(0), c_size_t(0)
+    status = lib.szs_rocm_fuzzy_scan_probe(queries_count, longest_query, text_length, ctypes.byref(piece), ctypes.byref(pieces),
+                                           ctypes.byref(workgroups), ctypes.byref(walked))
+    if status != 0:
+        raise StringZillasError(status, None)
+    return int(piece.value), int(pieces.value), int(workgroups.value), int(walked.value)
 
 
 PAIR_RULE_CHOOSE = 0xFFFFFFFF

@@ -359,6 +359,25 @@ int szs_hip_levenshtein_fuzzy_tile(szs_rerank_side_t const *queries, szs_rerank_
                                    uint32_t rows, uint64_t first_column, uint32_t columns, uint32_t segment, uint64_t *cells,
                                    uint64_t cells_stride, uint32_t *flags, unsigned long long *counters, void *stream);
 
+/**
+ *  The same distance of every query inside ONE long text (hip/myers_fuzzy_scan.hip; host/fuzzy_scan.c): the
+ *  text is cut into pieces of `piece` bytes, one one-wavefront workgroup per (row, 64 consecutive pieces) - the grid is
+ *  rows x ceil(ceil(text_length / piece) / 64) on x - and keys[r] = min(keys[r], distance << 32 | end) over the pieces of row r, by
+ *  one 64-bit atomic minimum a workgroup.  `keys`: `rows` words of device memory the caller has filled with 0xFF bytes on the same
+ *  stream; a row whose query has no bytes leaves its word alone.  `text`: `text_length` < 2^32 bytes the device can read.  A NULL
+ *  argument, `piece` 0, a text of 4 GiB or more and a grid of 2^31 workgroups or more are refused; no rows or no text launch
+ *  nothing.  Flags as above; `counters`: cells and bytes as walked - a piece behind the first starts up to 2 m bytes early - and
+ *  one pair per row with a non-empty query.
+ */
+int szs_hip_levenshtein_fuzzy_scan(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text,
+                                   uint64_t text_length, uint64_t piece, unsigned long long *keys, uint32_t *flags,
+                                   unsigned long long *counters, void *stream);
+/** Behind it on the same stream: distances[r] and (`ends` not NULL) ends[r] from keys[r] - (0, 0) for a query of no bytes, (m, 0)
+ *  where the word is still all ones, else (key >> 32, key & 0xFFFFFFFF) - by ordinary 8-byte stores. */
+int szs_hip_levenshtein_fuzzy_scan_emit(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows,
+                                        unsigned long long const *keys, uint64_t *distances, uint64_t *ends, uint32_t *flags,
+                                        void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {
@@ -397,6 +416,8 @@ enum {
                                own (host/rerank.c) | 1: the short kernel only, longer rows as engine calls (the A/B leg of the strips) */
     szs_knob_fuzzy_search_segment_k, /* -1 automatic | n: the candidates one workgroup of hip/myers_fuzzy_tile.hip scores for its row,
                                         rounded up to a multiple of 64 (host/fuzzy_search.c) */
+    szs_knob_fuzzy_scan_piece_k,     /* -1 automatic | n: the bytes of the text one lane of hip/myers_fuzzy_scan.hip owns, rounded up to a
+                                        multiple of 64, at least 64 (host/fuzzy_scan.c) */
     szs_knob_count_k
 };
 int szs_tuning_get(int knob);

@@ -420,4 +420,14 @@ sz_status_t szs_engine_fuzzy_search(szs_engine_s *engine, szs_scope_s *scope, sz
                                     size_t k, size_t *indices, size_t *distances, size_t *starts, size_t *ends, size_t row_stride,
                                     char const **error_message);
 
+/* ---- fuzzy scan (fuzzy_scan.c) ------------------------------------------------------------------------------------------ */
+
+/** The best match of every query inside ONE text of `text_length` < 2^32 bytes the device can read: vectors of `queries->count`
+ *  cells; `ends` may be NULL.  Unit-cost byte Levenshtein engines only.  Uses the engine's rerank buffers. */
+sz_status_t szs_engine_fuzzy_scan(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, void const *text, size_t text_length,
+                                  size_t *distances, size_t *ends, char const **error_message);
+/** The same call with `starts`, fuzzy find's.  All three outputs are required. */
+sz_status_t szs_engine_fuzzy_scan_spans(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, void const *text,
+                                        size_t text_length, size_t *distances, size_t *starts, size_t *ends, char const **error_message);
+
 #endif /* SZS_INTERNAL_H_ */

@@ -47,6 +47,7 @@ static struct {
     [szs_knob_top_k_tile_k] = {"top_k_tile", "SZS_ROCM_TOP_K_TILE"},
     [szs_knob_rerank_k] = {"rerank", "SZS_ROCM_RERANK"},
     [szs_knob_fuzzy_search_segment_k] = {"fuzzy_search_segment", "SZS_ROCM_FUZZY_SEARCH_SEGMENT"},
+    [szs_knob_fuzzy_scan_piece_k] = {"fuzzy_scan_piece", "SZS_ROCM_FUZZY_SCAN_PIECE"},
 };
 
 /** Text -> value.  -1 always means "automatic".  Tier names: lanes 0, systolic 1, chain 2; planner: host 0, device 1. */
