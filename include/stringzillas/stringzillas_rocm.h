@@ -25,6 +25,8 @@
  *    (csrc/host/fuzzy_search.c); szs_rocm_fuzzy_search_probe reports how a call would be cut.
  *  - szs_rocm_fuzzy_scan*       : the best match of every query inside ONE long text, the text cut over the device's lanes
  *    (csrc/host/fuzzy_scan.c); szs_rocm_fuzzy_scan_spans* add the starts, szs_rocm_fuzzy_scan_probe reports the cut.
+ *  - szs_rocm_fuzzy_scan_matches* : every end within a distance bound in that text, per query the count and the leftmost `limit`
+ *    hits (csrc/host/fuzzy_scan_matches.c).
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -363,6 +365,61 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_spans_u64tape(void *engine, szs_d
 SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_probe(sz_size_t queries_count, sz_size_t longest_query, sz_size_t text_length,
                                                      sz_size_t *piece, sz_size_t *pieces, sz_size_t *workgroups,
                                                      sz_size_t *walked_bytes_per_query);
+
+/**
+ *  Fuzzy scan MATCHES: where EVERY occurrence of a pattern lies in one long text, up to `max_distance` errors - fuzzy grep, all
+ *  primer sites, every misspelling of a name.  For every query q of m >= 1 bytes and the text of n = `text_length` bytes, with D
+ *  szs_rocm_fuzzy_find's unit-cost DP with a free start in the text, a HIT is a column j in [1, n] with D[m][j] <= max_distance
+ *  (column 0, the empty match, never is):
+ *      counts[q]                = the hits in the whole text - it may exceed `limit`;
+ *      ends[q * limit + i]      = the i-th hit in ascending j, for i < min(counts[q], limit): the exclusive byte offset at which the
+ *                                 match ends, as szs_rocm_fuzzy_scan reports ends;
+ *      distances[q * limit + i] = D[m][j] of that hit;
+ *  and every slot from min(counts[q], limit) to limit - 1 of both matrices holds 2^64 - 1, the empty slot (as szs_rocm_rerank's
+ *  indices).  `counts` is a vector of `queries.count` 8-byte cells, `distances` and `ends` are dense `queries.count` x `limit`
+ *  matrices of 8-byte cells: no strides.  A query of no bytes has count 0 and a row of empty slots; so has any query against an empty
+ *  text.  `max_distance` is any sz_size_t: D[m][j] <= m, so a bound of m or more makes every column 1 ... n a hit (the kernels
+ *  receive min(max_distance, 256)).  `limit` 0 is the counting form: only `counts` is written, `distances` and `ends` are not looked
+ *  at and may be NULL.  `limit` above 2^24 is refused - a choice, not a measurement: one row of outputs is then 256 MiB.
+ *
+ *  HOW, and why it is exact (csrc/hip/myers_fuzzy_matches.hip, csrc/host/fuzzy_scan_matches.c).  The text
+ *  is cut exactly as szs_rocm_fuzzy_scan cuts it: piece p owns columns (p P, min(n, (p + 1) P)] and its lane walks from
+ *  s = p P - min(p P, 2 m).  (1) A DP that starts at s chooses among fewer starts: its value L[j] >= D[m][j], no column is reported
+ *  that is not a hit.  (2) For an owned column j - s > 2 m or s = 0, and the start that attains D[m][j] lies within
+ *  m + D[m][j] <= 2 m bytes of j: L[j] = D[m][j], every hit is reported with its exact distance, by the one piece that owns it.
+ *  (3) A lane counts and reports owned columns only; its warm-up belongs to the piece before.  (A warm-up of m, enough for the
+ *  minimum of szs_rocm_fuzzy_scan, is NOT enough here.)  Two passes over the same bytes with the same arithmetic: the first counts
+ *  the hits per piece, prefix sums turn the counts into slots, the second stores the hits whose slot is below `limit`.  Every cell
+ *  has one writer: no allocation depends on the data, and the same call gives the same bytes every time.
+ *
+ *  LIMITS are szs_rocm_fuzzy_scan's: a unit-cost BYTE Levenshtein engine, queries of at most 256 bytes, a text below 4 GiB that the
+ *  device can read.  The outputs may live in device, pinned, unified or plain host memory (staged densely and copied home).
+ *
+ *  Refusals, in this order, before any launch and with nothing written: `text_length` >= 2^32 - sz_unexpected_dimensions_k;
+ *  `limit` > 2^24 - sz_unexpected_dimensions_k; an engine that is NULL, blank or not unit-cost byte Levenshtein - sz_status_unknown_k;
+ *  NULL `queries` - sz_status_unknown_k; zero queries - success, nothing is looked at; a NULL `counts` - sz_status_unknown_k; with
+ *  `limit` > 0 a NULL `distances` or `ends` - sz_status_unknown_k; a NULL `text` with `text_length` > 0, or a text the device cannot
+ *  read - sz_status_unknown_k; a query of more than 256 bytes - sz_unexpected_dimensions_k.  Synchronous, also when it fails.
+ *
+ *  Blocks of at most 2^20 queries - fewer where a staged block of outputs would pass 128 MiB an array, where rows x chunks of 64
+ *  pieces would pass 2^31 - 1 workgroups, or where the block's scratch (65 dwords per row and chunk, in the engine's staging
+ *  buffer) would pass 256 MiB; that figure too is a choice.  Per block the count, the offsets and - with `limit` > 0 - two fills and
+ *  the write, on the scope's stream.  The piece and the `fuzzy_scan_piece` knob are szs_rocm_fuzzy_scan's, and
+ *  szs_rocm_fuzzy_scan_probe reports them.  szs_rocm_last_call_profile: pairs = the queries of at least one byte (none for an empty
+ *  text), cells = m x the bytes walked by both passes, warm-ups included, launches = 2 per block with `limit` 0, else 3 (0 for an
+ *  empty text), kernel time = the event pair around them.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_matches(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, void const *text,
+                                                       sz_size_t text_length, sz_size_t max_distance, sz_size_t limit, sz_size_t *counts,
+                                                       sz_size_t *distances, sz_size_t *ends, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_matches_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                               void const *text, sz_size_t text_length, sz_size_t max_distance,
+                                                               sz_size_t limit, sz_size_t *counts, sz_size_t *distances, sz_size_t *ends,
+                                                               char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_matches_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                               void const *text, sz_size_t text_length, sz_size_t max_distance,
+                                                               sz_size_t limit, sz_size_t *counts, sz_size_t *distances, sz_size_t *ends,
+                                                               char const **error_message);
 
 /**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine

@@ -606,6 +606,80 @@ class _Engine:
             return out
         return tuple(vector.view(np.uint64) for vector in results[:, :rows].cpu().numpy())
 
+    def fuzzy_scan_matches(self, queries, text, max_distance, limit=64, device: Optional[DeviceScope] = None, out=None):
+        """EVERY end within `max_distance` edits of every query inside ONE long text (`szs_rocm_fuzzy_scan_matches_*`): returns
+        `(counts, distances, ends)` - a `uint64` vector of `len(queries)` and two `uint64` `(len(queries), limit)` arrays.  A hit of
+        `queries[q]` is an exclusive byte offset `j` in `[1, len(text)]` at which some substring of `text` ends that `max_distance` or
+        fewer edits turn into the query; `counts[q]` is their number in the whole text (it may exceed `limit`), `ends[q, i]` and
+        `distances[q, i]` the `i`-th of them in ascending `j` and its distance, and the slots behind hold 2**64 - 1.  `limit=0`
+        counts only: the two arrays have shape `(len(queries), 0)`.  `text` is what `fuzzy_scan` takes.  `out`: a triple of
+        contiguous NumPy arrays or torch tensors of 8-byte cells of those shapes, filled and returned.  Unit-cost byte Levenshtein
+        engines only, queries of at most 256 bytes, a text below 4 GiB, `limit` at most 2**24."""
+        import torch
+
+        names = ("out counts", "out distances", "out ends")
+        for value, name in ((max_distance, "max_distance"), (limit, "limit")):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < 2**64:
+                raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
+        max_distance, limit = int(max_distance), int(limit)
+        if limit > 2**24:
+            raise ValueError(f"limit must be at most 2**24, got {limit}")
+        queries = _as_strs(queries)
+        rows = len(queries)
+        is_tensor = type(text).__module__.partition(".")[0] == "torch" and hasattr(text, "data_ptr")
+        if is_tensor:
+            if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+                raise ValueError("`text` must be a contiguous vector of uint8")
+        elif isinstance(text, np.ndarray):
+            if text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
+                raise ValueError("`text` must be a contiguous vector of uint8")
+        elif isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        else:
+            raise ValueError(f"`text` must be bytes-like, a NumPy uint8 array or a torch uint8 tensor, got {type(text).__name__}")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != len(names):
+                raise ValueError("`out` must be a triple (counts, distances, ends)")
+            pointers = []
+            for array, name, wanted in zip(out, names, ((rows,), (rows, limit), (rows, limit))):
+                if isinstance(array, np.ndarray):
+                    shape, itemsize, dense, pointer = array.shape, array.dtype.itemsize, array.flags.c_contiguous, array.ctypes.data
+                elif type(array).__module__.partition(".")[0] == "torch" and hasattr(array, "data_ptr"):
+                    shape, itemsize, dense, pointer = tuple(array.shape), array.element_size(), array.is_contiguous(), array.data_ptr()
+                else:
+                    raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(array).__name__}")
+                if shape != wanted or itemsize != 8 or not dense:
+                    raise ValueError(f"`{name}` must be a contiguous array of shape {wanted} of 8-byte cells")
+                pointers.append(pointer if len(wanted) == 1 or limit else None)  # limit 0: the matrices are never looked at
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        for array, name in ((text, "text"),) + (tuple(zip(out, names)) if out is not None else ()):
+            if getattr(array, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
+                if array.device.index != gpu_device:
+                    raise ValueError(f"`{name}` is on {array.device}, the call runs on GPU {gpu_device}")
+                torch.cuda.current_stream(array.device).synchronize()  # torch's own stream may still be filling it
+        where = torch.device("cuda", gpu_device)
+        if not is_tensor:
+            text = torch.from_numpy(np.array(text, copy=True) if not text.flags.writeable else text)
+        if not text.is_cuda:  # host data: uploaded once
+            text = text.to(where)
+            torch.cuda.current_stream(where).synchronize()
+        if out is None:
+            results = (torch.empty(max(rows, 1), dtype=torch.int64, device=where),
+                       torch.empty((2, max(rows, 1), limit), dtype=torch.int64, device=where))
+            pointers = [results[0].data_ptr()] + [matrix.data_ptr() if limit else None for matrix in results[1]]
+
+        error = ctypes.c_char_p()
+        call = lib.szs_rocm_fuzzy_scan_matches_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_scan_matches_u32tape
+        q_tape = queries._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), text.data_ptr() if text.numel() else None, text.numel(), max_distance,
+                      limit, *pointers, ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        counts, matrices = results[0][:rows].cpu().numpy().view(np.uint64), results[1][:, :rows].cpu().numpy().view(np.uint64)
+        return counts, matrices[0], matrices[1]
+
     def __del__(self):
         handle = getattr(self, "handle", None)
         if handle and self._free is not None:

@@ -378,6 +378,29 @@ int szs_hip_levenshtein_fuzzy_scan_emit(szs_rerank_side_t const *queries, uint64
                                         unsigned long long const *keys, uint64_t *distances, uint64_t *ends, uint32_t *flags,
                                         void *stream);
 
+/**
+ *  Every end within a bound of every query inside ONE long text (hip/myers_fuzzy_matches.hip; host/fuzzy_scan_matches.c; DESIGN.md
+ *  section 4.12), in three launches on one stream over the scan's cut and grid - pieces of `piece` bytes, one one-wavefront workgroup
+ *  per (row, 64 consecutive pieces), chunks = ceil(ceil(text_length / piece) / 64).  A hit of row r is a column j in [1, text_length]
+ *  with D[m][j] <= `bound`.
+ *  COUNT: piece_counts[(r x chunks + chunk) x 64 + l] = the hits piece 64 chunk + l owns (0 beyond the pieces), chunk_counts[r x chunks
+ *  + chunk] = their sum.  Every cell of both is written: rows x chunks x 64 and rows x chunks dwords of device memory, nothing to clear.
+ *  OFFSETS: chunk_counts[r][*] becomes its exclusive prefix sums, counts[r] the row's total (8 bytes).
+ *  WRITE: for i < min(counts[r], limit), ends[r x limit + i] and distances[r x limit + i] = the i-th hit in ascending j and its
+ *  D[m][j]; no other slot is touched - the caller fills both matrices with 0xFF bytes on the same stream ahead of the launch.
+ *  `text`: `text_length` in [1, 2^32) bytes the device can read; `rows` >= 1; `limit` >= 1 for the write.  A NULL argument, `piece` 0,
+ *  an empty text or one of 4 GiB or more and a grid of 2^31 workgroups or more are refused.  Flags as above; `counters`: cells and
+ *  bytes as walked by both passes, one pair per row with a non-empty query (by the count pass).
+ */
+int szs_hip_levenshtein_fuzzy_matches_count(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text,
+                                            uint64_t text_length, uint64_t piece, uint32_t bound, uint32_t *piece_counts,
+                                            uint32_t *chunk_counts, uint32_t *flags, unsigned long long *counters, void *stream);
+int szs_hip_levenshtein_fuzzy_matches_offsets(uint32_t rows, uint64_t chunks, uint32_t *chunk_counts, uint64_t *counts, void *stream);
+int szs_hip_levenshtein_fuzzy_matches_write(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text,
+                                            uint64_t text_length, uint64_t piece, uint32_t bound, uint32_t limit,
+                                            uint32_t const *piece_counts, uint32_t const *chunk_counts, uint64_t *distances, uint64_t *ends,
+                                            uint32_t *flags, unsigned long long *counters, void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {

@@ -19,13 +19,8 @@
 
 static char const fuzzy_scan_long_query[] = "A query of more than 256 bytes: beyond what fuzzy scan takes";
 
-/** How a text of `n` bytes is cut for a block of `rows` rows: the bytes of a piece, the pieces, and the chunks of 64 pieces - the
- *  workgroups of a row.  Both constants are choices, not measurements. */
-typedef struct {
-    uint64_t piece, pieces, chunks;
-} fuzzy_scan_cut_t;
-
-static fuzzy_scan_cut_t fuzzy_scan_cut(size_t rows, uint64_t n) {
+/* (declared in rerank_internal.h: szs_rocm_fuzzy_scan_matches* - fuzzy_scan_matches.c - cuts its text by the same rule) */
+fuzzy_scan_cut_t fuzzy_scan_cut(size_t rows, uint64_t n) {
     uint64_t const wanted = (uint64_t)SZS_FUZZY_SCAN_WAVES * SZS_FUZZY_SCAN_FILLS;
     uint64_t const chunks_wanted = (wanted + rows - 1) / rows, lanes_wanted = chunks_wanted * SZS_FUZZY_SCAN_LANES;
     uint64_t piece = (n + lanes_wanted - 1) / lanes_wanted;

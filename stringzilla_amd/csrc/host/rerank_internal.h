@@ -108,6 +108,16 @@ sz_status_t szs_fuzzy_find_prepare(szs_fuzzy_find_call_t *call, szs_input_t cons
  *  hip/myers_fuzzy_spans.hip behind it; drains the stream and adds the block to `listed.total`. */
 sz_status_t szs_fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size_t rows, hipError_t *hip_error, char const **error_message);
 
+/* ---- fuzzy scan's cut (fuzzy_scan.c), which fuzzy scan matches (fuzzy_scan_matches.c) shares -------------------------------------- */
+
+/** How a text of `n` bytes is cut for a block of `rows` rows: the bytes of a piece, the pieces, and the chunks of 64 pieces - the
+ *  workgroups of a row.  Both constants are choices, not measurements. */
+typedef struct {
+    uint64_t piece, pieces, chunks;
+} fuzzy_scan_cut_t;
+
+fuzzy_scan_cut_t fuzzy_scan_cut(size_t rows, uint64_t n);
+
 /**
  *  The rows of a block whose query has at most SZS_RERANK_LONGEST_QUERY bytes into `order`, longest query first (a counting sort of
  *  the lengths 256 ... 0): the rows of a wavefront then share a width.  `lengths`: the block's, ~0 where no kernel takes the row.

@@ -430,4 +430,13 @@ sz_status_t szs_engine_fuzzy_scan(szs_engine_s *engine, szs_scope_s *scope, szs_
 sz_status_t szs_engine_fuzzy_scan_spans(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, void const *text,
                                         size_t text_length, size_t *distances, size_t *starts, size_t *ends, char const **error_message);
 
+/* ---- fuzzy scan matches (fuzzy_scan_matches.c) -------------------------------------------------------------------------- */
+
+/** Every end within `max_distance` of every query inside ONE text: `counts` of `queries->count` cells, `distances` and `ends` dense
+ *  `queries->count` x `limit` matrices with the leftmost `limit` hits a row (`limit` 0: neither is looked at).  Unit-cost byte
+ *  Levenshtein engines only.  Uses the engine's rerank buffers. */
+sz_status_t szs_engine_fuzzy_scan_matches(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, void const *text,
+                                          size_t text_length, size_t max_distance, size_t limit, size_t *counts, size_t *distances,
+                                          size_t *ends, char const **error_message);
+
 #endif /* SZS_INTERNAL_H_ */
