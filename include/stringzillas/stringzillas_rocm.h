@@ -27,6 +27,8 @@
  *    (csrc/host/fuzzy_scan.c); szs_rocm_fuzzy_scan_spans* add the starts, szs_rocm_fuzzy_scan_probe reports the cut.
  *  - szs_rocm_fuzzy_scan_matches* : every end within a distance bound in that text, per query the count and the leftmost `limit`
  *    hits (csrc/host/fuzzy_scan_matches.c).
+ *  - szs_rocm_fuzzy_scan_occurrences* : one span per occurrence in that text - the first column of every valley floor of the DP's
+ *    bottom row within the bound, with its distance and where the match starts (csrc/host/fuzzy_scan_occurrences.c).
  *  - szs_rocm_fingerprint_matches, szs_rocm_fingerprint_top_k : what the MinHash fingerprints of szs_fingerprints_* are for - the
  *    equal dimensions of every pair of fingerprints (divided by `dimensions`: the Jaccard estimate) and the k candidates with the
  *    most of them per query, for near-duplicate search at `dimensions` compares per pair (csrc/host/fingerprint_search.c).
@@ -420,6 +422,63 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_matches_u64tape(void *engine, szs
                                                                void const *text, sz_size_t text_length, sz_size_t max_distance,
                                                                sz_size_t limit, sz_size_t *counts, sz_size_t *distances, sz_size_t *ends,
                                                                char const **error_message);
+
+/**
+ *  Fuzzy scan OCCURRENCES: one span per occurrence instead of every end column - what to highlight, what to cut out.  A real
+ *  occurrence shows up in szs_rocm_fuzzy_scan_matches as a cluster of adjacent hits j - 1, j, j + 1, ...; this call reports one end
+ *  per cluster and where the match that ends there starts.  m, n, D and `max_distance` mean exactly what they mean there (D[m][0] = m).
+ *  Column j in [1, n] is an OCCURRENCE END of query q iff all three hold:
+ *      (1) D[m][j] <= max_distance;   (2) D[m][j] < D[m][j - 1];   (3) j == n or D[m][j] <= D[m][j + 1]
+ *  - the first column of a valley floor of the bottom row, within the bound.  A plateau reports its leftmost column only (the
+ *  leftmost-ending convention of szs_rocm_fuzzy_find); a step down that keeps descending is not reported; (2) and (3) look at the
+ *  neighbours whether or not those are within the bound.  The spans of different occurrences MAY OVERLAP: a non-overlapping selection
+ *  is not promised and is left to the caller.
+ *      counts[q]                = the occurrence ends in the whole text - it may exceed `limit`;
+ *      ends[q * limit + i]      = the i-th of them in ascending j, for i < min(counts[q], limit);
+ *      distances[q * limit + i] = D[m][j] of it;
+ *      starts[q * limit + i]    = j - t*, t* the smallest t <= min(j, m + D[m][j]) with lev(query, text[j - t : j]) == D[m][j] - the
+ *                                 definition of szs_rocm_fuzzy_find_spans; such a t exists because D[m][j] is the minimum over all
+ *                                 starts, and |t - m| <= D[m][j] for any t that attains it;
+ *  and every slot from min(counts[q], limit) to limit - 1 of the three matrices holds 2^64 - 1.  Shapes, the empty query, the empty
+ *  text, any `max_distance` and the `limit` are szs_rocm_fuzzy_scan_matches'.  `limit` 0 counts only: the matrices are not looked at
+ *  and may be NULL.  `starts` may be NULL with any `limit`: no reverse pass is launched.
+ *
+ *  Three facts (tests/test_fuzzy_scan_occurrences_model.py; tests/test_gpu_fuzzy_scan_occurrences.py).  (a) Every occurrence end is
+ *  a hit of szs_rocm_fuzzy_scan_matches for the same bound, with the same distance: (1) is that call's condition.  (b) If the best
+ *  distance d* of szs_rocm_fuzzy_scan satisfies d* <= max_distance and d* < m, its (d*, end) is an occurrence, and the leftmost one
+ *  of minimum distance: the leftmost global minimum of the bottom row is below everything to its left - D[m][0] = m > d* included, so
+ *  it is not column 0 - which is (2), and at most everything to its right, which is (3).  (c) A query that matches nothing better
+ *  than m everywhere has no occurrence, even at max_distance >= m: the bottom row never goes below D[m][0] = m and never above it.
+ *
+ *  HOW (csrc/hip/myers_fuzzy_occurrences.hip, csrc/host/fuzzy_scan_occurrences.c).  The cut, the warm-up of
+ *  min(p P, 2 m) bytes and the two passes over a fixed capacity are szs_rocm_fuzzy_scan_matches'.  Proof sketch of the rule under the
+ *  cut: a lane whose piece is not the last walks one column behind its last owned column, (p + 1) P + 1, which is exact as owned
+ *  columns are (it lies further from the lane's start s); the left neighbour of the first owned column, p P, is 2 m columns into the
+ *  walk or s = 0, and the start that attains D[m][p P] lies within m + D <= 2 m bytes of it, at or behind s.  So a lane sees the exact
+ *  bottom row on its owned columns and one column to each side, and decides column c - 1 at column c; the lane of the last piece
+ *  decides column n behind its walk.  The starts are szs_rocm_fuzzy_find_spans' reverse pass over every filled slot: the reversed
+ *  query over at most m + D <= 512 bytes that end at `end`.  No atomics on outputs, one writer a slot, the same bytes every call.
+ *
+ *  LIMITS, refusals and their order, the memory kinds of the outputs, blocks (also: rows x ceil(limit / 64) within 2^31 - 1
+ *  workgroups) and the `fuzzy_scan_piece` knob are szs_rocm_fuzzy_scan_matches'; the messages name this call.
+ *  szs_rocm_last_call_profile: pairs as there; cells = m x the bytes walked by every pass that ran - warm-ups, tail columns and the
+ *  windows of the reverse pass included; launches = 2 per block with `limit` 0, 3 with a limit and no `starts`, 4 with `starts` (0
+ *  for an empty text).
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_occurrences(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                                           void const *text, sz_size_t text_length, sz_size_t max_distance, sz_size_t limit,
+                                                           sz_size_t *counts, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                           char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_occurrences_u32tape(void *engine, szs_device_scope_t device,
+                                                                   sz_sequence_u32tape_t const *queries, void const *text,
+                                                                   sz_size_t text_length, sz_size_t max_distance, sz_size_t limit,
+                                                                   sz_size_t *counts, sz_size_t *distances, sz_size_t *starts,
+                                                                   sz_size_t *ends, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_scan_occurrences_u64tape(void *engine, szs_device_scope_t device,
+                                                                   sz_sequence_u64tape_t const *queries, void const *text,
+                                                                   sz_size_t text_length, sz_size_t max_distance, sz_size_t limit,
+                                                                   sz_size_t *counts, sz_size_t *distances, sz_size_t *starts,
+                                                                   sz_size_t *ends, char const **error_message);
 
 /**
  *  Fingerprint search: consumes the `min_hashes` matrices that `szs_fingerprints_*` produce.  `engine` is a fingerprints engine

@@ -615,9 +615,28 @@ class _Engine:
         counts only: the two arrays have shape `(len(queries), 0)`.  `text` is what `fuzzy_scan` takes.  `out`: a triple of
         contiguous NumPy arrays or torch tensors of 8-byte cells of those shapes, filled and returned.  Unit-cost byte Levenshtein
         engines only, queries of at most 256 bytes, a text below 4 GiB, `limit` at most 2**24."""
+        return self._fuzzy_scan_columns("szs_rocm_fuzzy_scan_matches", ("counts", "distances", "ends"), queries, text, max_distance, limit,
+                                        device, out)
+
+    def fuzzy_scan_occurrences(self, queries, text, max_distance, limit=64, starts=True, device: Optional[DeviceScope] = None, out=None):
+        """ONE span per occurrence of every query inside ONE long text (`szs_rocm_fuzzy_scan_occurrences_*`): returns
+        `(counts, distances, starts, ends)` - a `uint64` vector of `len(queries)` and three `uint64` `(len(queries), limit)` arrays;
+        `starts=False` returns `(counts, distances, ends)` and launches no reverse pass.  With `D[j]` the fewest edits between
+        `queries[q]` and a substring of `text` that ends at byte offset `j` (`D[0]` = the query's length), `j` in `[1, len(text)]` is
+        an occurrence end iff `D[j] <= max_distance`, `D[j] < D[j - 1]` and `j == len(text) or D[j] <= D[j + 1]`: the first column of a
+        valley floor - one per cluster of `fuzzy_scan_matches` hits, the leftmost of a plateau.  `counts[q]` is their number in the whole
+        text (it may exceed `limit`); `ends[q, i]`, `distances[q, i]` and `starts[q, i]` describe the `i`-th of them in ascending
+        `j`: `text[starts[q, i]:ends[q, i]]` is the shortest substring ending there at that distance.  Spans of different occurrences
+        may overlap.  The slots behind hold 2**64 - 1; `limit=0` counts only: the arrays have shape `(len(queries), 0)`.  `text`,
+        `out` (here a quadruple, or a triple with `starts=False`) and the limits are `fuzzy_scan_matches`'."""
+        names = ("counts", "distances", "starts", "ends") if starts else ("counts", "distances", "ends")
+        return self._fuzzy_scan_columns("szs_rocm_fuzzy_scan_occurrences", names, queries, text, max_distance, limit, device, out)
+
+    def _fuzzy_scan_columns(self, entry, names, queries, text, max_distance, limit, device, out):
+        """What `fuzzy_scan_matches` and `fuzzy_scan_occurrences` share: the checks, the text on the device, a vector of counts and
+        `len(names) - 1` matrices of `limit` slots a row behind `entry`'s tape forms (a missing `starts` goes as NULL)."""
         import torch
 
-        names = ("out counts", "out distances", "out ends")
         for value, name in ((max_distance, "max_distance"), (limit, "limit")):
             if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < 2**64:
                 raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
@@ -639,21 +658,21 @@ class _Engine:
             raise ValueError(f"`text` must be bytes-like, a NumPy uint8 array or a torch uint8 tensor, got {type(text).__name__}")
         if out is not None:
             if not isinstance(out, (tuple, list)) or len(out) != len(names):
-                raise ValueError("`out` must be a triple (counts, distances, ends)")
+                raise ValueError(f"`out` must be a tuple ({', '.join(names)})")
             pointers = []
-            for array, name, wanted in zip(out, names, ((rows,), (rows, limit), (rows, limit))):
+            for array, name, wanted in zip(out, names, ((rows,),) + ((rows, limit),) * (len(names) - 1)):
                 if isinstance(array, np.ndarray):
                     shape, itemsize, dense, pointer = array.shape, array.dtype.itemsize, array.flags.c_contiguous, array.ctypes.data
                 elif type(array).__module__.partition(".")[0] == "torch" and hasattr(array, "data_ptr"):
                     shape, itemsize, dense, pointer = tuple(array.shape), array.element_size(), array.is_contiguous(), array.data_ptr()
                 else:
-                    raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(array).__name__}")
+                    raise ValueError(f"`out {name}` must be a NumPy array or a torch tensor, got {type(array).__name__}")
                 if shape != wanted or itemsize != 8 or not dense:
-                    raise ValueError(f"`{name}` must be a contiguous array of shape {wanted} of 8-byte cells")
+                    raise ValueError(f"`out {name}` must be a contiguous array of shape {wanted} of 8-byte cells")
                 pointers.append(pointer if len(wanted) == 1 or limit else None)  # limit 0: the matrices are never looked at
         scope = device or self._scope or _get_default_scope()
         gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for array, name in ((text, "text"),) + (tuple(zip(out, names)) if out is not None else ()):
+        for array, name in ((text, "text"),) + (tuple(zip(out, ("out " + name for name in names))) if out is not None else ()):
             if getattr(array, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
                 if array.device.index != gpu_device:
                     raise ValueError(f"`{name}` is on {array.device}, the call runs on GPU {gpu_device}")
@@ -666,11 +685,13 @@ class _Engine:
             torch.cuda.current_stream(where).synchronize()
         if out is None:
             results = (torch.empty(max(rows, 1), dtype=torch.int64, device=where),
-                       torch.empty((2, max(rows, 1), limit), dtype=torch.int64, device=where))
+                       torch.empty((len(names) - 1, max(rows, 1), limit), dtype=torch.int64, device=where))
             pointers = [results[0].data_ptr()] + [matrix.data_ptr() if limit else None for matrix in results[1]]
 
         error = ctypes.c_char_p()
-        call = lib.szs_rocm_fuzzy_scan_matches_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_scan_matches_u32tape
+        call = getattr(lib, entry + ("_u64tape" if queries.wide_offsets else "_u32tape"))
+        if entry == "szs_rocm_fuzzy_scan_occurrences" and "starts" not in names:
+            pointers = pointers[:2] + [None] + pointers[2:]  # (counts, distances, no starts, ends)
         q_tape = queries._tape(gpu_device)
         status = call(self.handle, scope.handle, ctypes.byref(q_tape), text.data_ptr() if text.numel() else None, text.numel(), max_distance,
                       limit, *pointers, ctypes.byref(error))
@@ -678,7 +699,7 @@ class _Engine:
         if out is not None:
             return out
         counts, matrices = results[0][:rows].cpu().numpy().view(np.uint64), results[1][:, :rows].cpu().numpy().view(np.uint64)
-        return counts, matrices[0], matrices[1]
+        return (counts,) + tuple(matrices)
 
     def __del__(self):
         handle = getattr(self, "handle", None)

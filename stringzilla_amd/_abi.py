@@ -89,6 +89,8 @@ _FUZZY_SEARCH = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_voi
 _FUZZY_SCAN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ERR])
 _FUZZY_SCAN_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
 _FUZZY_SCAN_MATCHES = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
+_FUZZY_SCAN_OCCURRENCES = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   ERR])
 
 SIGNATURES = {
     "szs_version_major": (c_int, []), "szs_version_minor": (c_int, []), "szs_version_patch": (c_int, []),
@@ -152,6 +154,8 @@ SIGNATURES = {
     "szs_rocm_fuzzy_scan_spans_u64tape": _FUZZY_SCAN_SPANS,
     "szs_rocm_fuzzy_scan_matches": _FUZZY_SCAN_MATCHES, "szs_rocm_fuzzy_scan_matches_u32tape": _FUZZY_SCAN_MATCHES,
     "szs_rocm_fuzzy_scan_matches_u64tape": _FUZZY_SCAN_MATCHES,
+    "szs_rocm_fuzzy_scan_occurrences": _FUZZY_SCAN_OCCURRENCES, "szs_rocm_fuzzy_scan_occurrences_u32tape": _FUZZY_SCAN_OCCURRENCES,
+    "szs_rocm_fuzzy_scan_occurrences_u64tape": _FUZZY_SCAN_OCCURRENCES,
     "szs_rocm_fuzzy_scan_probe": (c_int, [c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
                                           ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "szs_rocm_rerank_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -401,6 +401,31 @@ int szs_hip_levenshtein_fuzzy_matches_write(szs_rerank_side_t const *queries, ui
                                             uint32_t const *piece_counts, uint32_t const *chunk_counts, uint64_t *distances, uint64_t *ends,
                                             uint32_t *flags, unsigned long long *counters, void *stream);
 
+/**
+ *  ONE end per occurrence of every query inside that text, and where each starts (hip/myers_fuzzy_occurrences.hip;
+ *  host/fuzzy_scan_occurrences.c).  An occurrence end of row r is a column j in [1, text_length] with
+ *  D[m][j] <= `bound`, D[m][j] < D[m][j - 1] and (j == text_length or D[m][j] <= D[m][j + 1]).  COUNT and WRITE are the two launches
+ *  above with "occurrence" in place of "hit": the same arguments, scratch, grid, refusals, flags and counters - a piece that is not
+ *  the last walks one column more - and szs_hip_levenshtein_fuzzy_matches_offsets runs between them as it is.
+ *  STARTS, behind the write on the same stream: one one-wavefront workgroup per (row, 64 consecutive slots), the grid
+ *  rows x ceil(limit / 64) on x, at most 2^31 - 1.  For every slot i < min(counts[r], limit) that does not hold 2^64 - 1 in both
+ *  matrices: starts[r x limit + i] = end - t*, t* the smallest t in [0, min(end, m + distance)] for which the global distance of the
+ *  query and text[end - t : end] is `distance`.  No other slot is touched.  A `distance` above the query's length or an `end` above
+ *  `text_length` is never used to address anything and sets `flags[SZS_RERANK_FLAG_TAPE]`.  `counters`: [1] += m x the window's bytes,
+ *  [2] += m + the window's bytes; [0] is left alone.
+ */
+int szs_hip_levenshtein_fuzzy_occurrences_count(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text,
+                                                uint64_t text_length, uint64_t piece, uint32_t bound, uint32_t *piece_counts,
+                                                uint32_t *chunk_counts, uint32_t *flags, unsigned long long *counters, void *stream);
+int szs_hip_levenshtein_fuzzy_occurrences_write(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text,
+                                                uint64_t text_length, uint64_t piece, uint32_t bound, uint32_t limit,
+                                                uint32_t const *piece_counts, uint32_t const *chunk_counts, uint64_t *distances,
+                                                uint64_t *ends, uint32_t *flags, unsigned long long *counters, void *stream);
+int szs_hip_levenshtein_fuzzy_occurrence_starts(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text,
+                                                uint64_t text_length, uint32_t limit, uint64_t const *counts, uint64_t const *distances,
+                                                uint64_t const *ends, uint64_t *starts, uint32_t *flags, unsigned long long *counters,
+                                                void *stream);
+
 /* ---- tuning knobs (host/tuning.c): read from the environment ONCE at load, changed only by szs_rocm_tuning_set -------- */
 
 enum {

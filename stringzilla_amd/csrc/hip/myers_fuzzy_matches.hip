@@ -3,7 +3,8 @@
  *  host/fuzzy_scan_matches.c): a hit is a column j in [1, n] with D[m][j] <= bound, D the unit-cost DP with
  *  a free start in the text; per query the number of hits in the whole text and the leftmost `limit` of them as (end, distance).
  *  The distance, its table and a lane's walk are hip/fuzzy_core.hpp's and hip/rerank_core.hpp's, unchanged; the cut of the text and
- *  the schedule are hip/myers_fuzzy_scan.hip's.  This file's own is the output: a fixed capacity, filled in two passes.
+ *  the schedule are hip/myers_fuzzy_scan.hip's; a lane's piece, the counters and the grid are hip/fuzzy_pieces.hpp's, shared with
+ *  hip/myers_fuzzy_occurrences.hip.  This file's own is the output: a fixed capacity, filled in two passes.
  *
  *  - Piece p owns columns (p P, min(n, (p + 1) P)].  The lane that takes it walks from s = p P - warm, warm = min(p P, 2 m): its DP
  *    has a free start at s instead of at 0, so every value L[j] it sees is >= D[m][j] (fewer starts to choose from) - no column is
@@ -27,37 +28,9 @@
  *  - Every slot and every count has one writer and a value that does not depend on the order of anything: the same bytes every run.
  *  - Counters: cells and bytes as walked in both passes; one pair per row with a non-empty query, by chunk 0 of the count pass alone.
  */
-#include "fuzzy_core.hpp"
+#include "fuzzy_pieces.hpp"
 
 namespace szs_hip {
-
-/** Inclusive prefix sums over the 64 lanes of a wavefront. */
-__device__ __forceinline__ u32 wave_prefix_u32(u32 value) {
-    u32 const lane = threadIdx.x % wave_size_k;
-#pragma unroll
-    for (u32 offset = 1; offset < wave_size_k; offset <<= 1) {
-        u32 const other = (u32)__shfl_up((int)value, offset, 64);
-        if (lane >= offset) value += other;
-    }
-    return value;
-}
-
-/** What lane l of `chunk` walks: piece p = 64 chunk + l from `first` = p P - warm over `walked` = warm + own bytes. */
-struct matches_piece_t {
-    bool inside; // p < pieces
-    u32 warm, first, walked;
-};
-
-__device__ __forceinline__ matches_piece_t matches_piece(u32 query_length, u32 text_length, u64 piece, u32 pieces, u32 chunk) {
-    u64 const p = (u64)chunk * wave_size_k + threadIdx.x;
-    matches_piece_t lane;
-    lane.inside = p < pieces;
-    u64 const from = lane.inside ? p * piece : 0; // below text_length: pieces = ceil(text_length / piece)
-    lane.warm = from < 2u * query_length ? (u32)from : 2u * query_length;
-    u32 const own = lane.inside ? (u32)(text_length - from < piece ? text_length - from : piece) : 0u;
-    lane.first = (u32)from - lane.warm, lane.walked = lane.inside ? own + lane.warm : 0u; // first + walked <= text_length
-    return lane;
-}
 
 /** One lane's walk of its piece against the row's table: `on_hit(column_end, score)` at every OWNED column whose bottom-row score is
  *  within `bound`; `keep_going()` as listed_walk asks it.  Returns the columns the lane took. */
@@ -83,14 +56,6 @@ __device__ __forceinline__ u32 matches_walk(u32 const *table, u32 query_length, 
         },
         keep_going);
     return taken;
-}
-
-/** The counters of a walk: cells and bytes as walked; the query read once a workgroup; the pair by chunk 0 of the count pass. */
-__device__ __forceinline__ void matches_counted(listed_row_t const &row, bool live, u32 taken, bool with_pairs, unsigned long long *counters) {
-    listed_counters_t counted;
-    if (live) counted.cells = (u64)row.query_length * taken, counted.bytes = taken;
-    if (threadIdx.x == 0) counted.bytes += row.query_length, counted.pairs = with_pairs;
-    counted.land(counters, with_pairs);
 }
 
 template <int words_>
@@ -196,15 +161,6 @@ __global__ __launch_bounds__(64) void levenshtein_fuzzy_matches_write_kernel(szs
         matches_write_row<decltype(width)::value>(fuzzy_matches_table, row, text, text_length, piece, pieces, chunk, bound, limit,
                                                   before + upto - hits, hits, distances, ends, counters);
     });
-}
-
-/** The grid both walking passes share; false: arguments no launch takes. */
-static bool matches_grid(szs_rerank_side_t const *queries, uint64_t first_query, uint32_t rows, void const *text, uint64_t text_length,
-                         uint64_t piece, u64 &pieces, u64 &chunks) {
-    if (!queries || !piece || !text || !text_length || text_length > 0xFFFFFFFFull || !rows || first_query + rows > queries->count) return false;
-    pieces = (text_length + piece - 1) / piece; // below 2^32
-    chunks = (pieces + wave_size_k - 1) / wave_size_k;
-    return (u64)rows * chunks <= 0x7FFFFFFFull;
 }
 
 } // namespace szs_hip

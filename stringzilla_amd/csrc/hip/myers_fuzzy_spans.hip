@@ -24,10 +24,12 @@
  *  caller can reach, so before they address anything: d <= m and end <= the candidate's length, else SZS_RERANK_FLAG_TAPE and a
  *  frozen lane.  The counters gain m x T cells and m + T bytes per pair; pairs are counted by the first kernel only.
  */
-#include "rerank_core.hpp"
+#include "fuzzy_core.hpp"
 
 namespace szs_hip {
 
+/** (the table and a lane's walk are hip/fuzzy_core.hpp's fuzzy_reversed_table and fuzzy_start_walk: hip/myers_fuzzy_occurrences.hip
+ *  runs the same pass over a matrix of slots in one text) */
 template <int words_, int lanes_>
 __device__ __forceinline__ void fuzzy_starts_rows(u32 *table, listed_row_t const &row, szs_rerank_side_t const &candidates,
                                                   u64 const *__restrict__ indices, u64 indices_stride, u64 k,
@@ -35,9 +37,7 @@ __device__ __forceinline__ void fuzzy_starts_rows(u32 *table, listed_row_t const
                                                   u64 outputs_stride, u32 *flags, unsigned long long *counters) {
     u32 const sub = threadIdx.x % lanes_;
     u32 const query_length = row.query_length;
-    u32 const pad = 32u * words_ - query_length; // phantom low rows of THIS row (a row without a query: all of them)
-    // the REVERSED pattern: the query's last byte is the first real row
-    listed_table<words_, lanes_>(table, row, [](int) { return 0u; }, [&](u32 i) { return pad + (query_length - 1u - i); });
+    fuzzy_reversed_table<words_, lanes_>(table, row); // (a row without a query: phantom rows only)
 
     listed_counters_t counted;
 #pragma unroll 1
@@ -57,22 +57,7 @@ __device__ __forceinline__ void fuzzy_starts_rows(u32 *table, listed_row_t const
             }
         }
 
-        u32 vp[words_], vn[words_];
-#pragma unroll
-        for (int w = 0; w < words_; ++w) vp[w] = rerank_bits_in_word(pad, 32u * words_, w), vn[w] = 0;
-        u32 score = query_length, best = query_length, pos = 0;
-        listed_walk(
-            text_stream_backward_t(address + (end - window), window), window, live,
-            [&](u32 symbol, u32 taken) {
-                u32 eq[words_];
-                load_match_masks<words_, byte_rows_k>(table, symbol, eq);
-                u32 const top = myers_prefix_column<words_>(vp, vn, eq);
-                score += (top & 1u) - (top >> 1);
-                if (score < best) best = score, pos = taken; // strictly smaller: the smallest t
-            },
-            // a lane is open while its best is above d; with none open in the wavefront no `pos` can move any more
-            [&]() { return __builtin_amdgcn_ballot_w64(live && best != distance) != 0ull; });
-
+        u32 const pos = fuzzy_start_walk<words_>(table, query_length, address, end, window, distance, live);
         if (live) {
             starts[at] = end - pos;
             counted.add(query_length, window);

@@ -515,6 +515,32 @@ sz_status_t szs_rocm_fuzzy_scan_matches_u64tape(void *engine, szs_device_scope_t
     SZS_FUZZY_SCAN_MATCHES_BODY(input_from_u64tape)
 }
 
+/* ---- fuzzy scan occurrences (host/fuzzy_scan_occurrences.c) ----------------------------------------------------------- */
+
+#define SZS_FUZZY_SCAN_OCCURRENCES_BODY(MAKE_INPUT)                                                                                \
+    szs_input_t query_input;                                                                                                       \
+    if (queries) query_input = MAKE_INPUT(queries);                                                                                \
+    return szs_engine_fuzzy_scan_occurrences((szs_engine_s *)engine, (szs_scope_s *)device, queries ? &query_input : NULL, text,   \
+                                             text_length, max_distance, limit, counts, distances, starts, ends, error_message);
+
+sz_status_t szs_rocm_fuzzy_scan_occurrences(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, void const *text,
+                                            sz_size_t text_length, sz_size_t max_distance, sz_size_t limit, sz_size_t *counts,
+                                            sz_size_t *distances, sz_size_t *starts, sz_size_t *ends, char const **error_message) {
+    SZS_FUZZY_SCAN_OCCURRENCES_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_fuzzy_scan_occurrences_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                    void const *text, sz_size_t text_length, sz_size_t max_distance, sz_size_t limit,
+                                                    sz_size_t *counts, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                    char const **error_message) {
+    SZS_FUZZY_SCAN_OCCURRENCES_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_fuzzy_scan_occurrences_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                    void const *text, sz_size_t text_length, sz_size_t max_distance, sz_size_t limit,
+                                                    sz_size_t *counts, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                    char const **error_message) {
+    SZS_FUZZY_SCAN_OCCURRENCES_BODY(input_from_u64tape)
+}
+
 /* ---- fingerprint search (host/fingerprint_search.c) ------------------------------------------------------------------- */
 
 sz_status_t szs_rocm_fingerprint_matches(szs_fingerprints_t engine, szs_device_scope_t device, sz_u32_t const *query_hashes,

@@ -11,11 +11,8 @@
  */
 #include "rerank_internal.h"
 
-#define SZS_FUZZY_MATCHES_MOST_LIMIT ((size_t)1 << 24)          /* a choice, not a measurement: one row of outputs is then 256 MiB */
-#define SZS_FUZZY_MATCHES_SCRATCH_BYTES ((uint64_t)256 << 20)   /* a block's piece and chunk counts; a choice, not a measurement */
-#define SZS_FUZZY_MATCHES_MOST_WORKGROUPS ((uint64_t)0x7FFFFFFF) /* the grid of a launch */
-#define SZS_FUZZY_MATCHES_LANES 64u                              /* the pieces of a chunk */
-
+/* (SZS_FUZZY_MATCHES_*, fuzzy_matches_scratch and fuzzy_matches_block_rows are declared in rerank_internal.h:
+ * szs_rocm_fuzzy_scan_occurrences* - fuzzy_scan_occurrences.c - has the same scratch and the same blocks) */
 static char const fuzzy_matches_long_query[] = "A query of more than 256 bytes: beyond what fuzzy scan matches takes";
 
 /** What the blocks of one call share. */
@@ -33,13 +30,13 @@ typedef struct {
 } fuzzy_matches_call_t;
 
 /** The bytes of a block's scratch, a multiple of 16. */
-static uint64_t fuzzy_matches_scratch(uint64_t rows, uint64_t chunks) {
+uint64_t fuzzy_matches_scratch(uint64_t rows, uint64_t chunks) {
     return (rows * chunks * (SZS_FUZZY_MATCHES_LANES + 1) * sizeof(uint32_t) + 15) & ~(uint64_t)15;
 }
 
 /** The rows of a block: listed_pairs.c's with `limit` slots a row, fewer where rows x chunks would pass the grid's 2^31 - 1 workgroups,
  *  and fewer again where the block's scratch would pass SZS_FUZZY_MATCHES_SCRATCH_BYTES.  At least one. */
-static size_t fuzzy_matches_block_rows(size_t q_count, size_t limit, int within_stage_budget, uint64_t n, fuzzy_scan_cut_t *cut) {
+size_t fuzzy_matches_block_rows(size_t q_count, size_t limit, int within_stage_budget, uint64_t n, fuzzy_scan_cut_t *cut) {
     size_t block = szs_listed_block_rows(q_count, limit ? limit : 1, within_stage_budget);
     *cut = fuzzy_scan_cut(block, n);
     if (!cut->chunks) return block;

@@ -118,6 +118,19 @@ typedef struct {
 
 fuzzy_scan_cut_t fuzzy_scan_cut(size_t rows, uint64_t n);
 
+/* ---- the blocks and the scratch of fuzzy scan matches (fuzzy_scan_matches.c), which fuzzy scan occurrences (fuzzy_scan_occurrences.c)
+ *      shares --------------------------------------------------------------------------------------------------------------------- */
+
+#define SZS_FUZZY_MATCHES_MOST_LIMIT ((size_t)1 << 24)          /* a choice, not a measurement: one row of outputs is then 256 MiB */
+#define SZS_FUZZY_MATCHES_SCRATCH_BYTES ((uint64_t)256 << 20)   /* a block's piece and chunk counts; a choice, not a measurement */
+#define SZS_FUZZY_MATCHES_MOST_WORKGROUPS ((uint64_t)0x7FFFFFFF) /* the grid of a launch */
+#define SZS_FUZZY_MATCHES_LANES 64u                              /* the pieces of a chunk */
+
+/** The bytes of a block's scratch - 64 piece counts and one chunk count per (row, chunk) - a multiple of 16. */
+uint64_t fuzzy_matches_scratch(uint64_t rows, uint64_t chunks);
+/** The rows of a block with `limit` slots a row, at least one, and the cut of a text of `n` bytes for them. */
+size_t fuzzy_matches_block_rows(size_t q_count, size_t limit, int within_stage_budget, uint64_t n, fuzzy_scan_cut_t *cut);
+
 /**
  *  The rows of a block whose query has at most SZS_RERANK_LONGEST_QUERY bytes into `order`, longest query first (a counting sort of
  *  the lengths 256 ... 0): the rows of a wavefront then share a width.  `lengths`: the block's, ~0 where no kernel takes the row.

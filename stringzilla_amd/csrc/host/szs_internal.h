@@ -439,4 +439,14 @@ sz_status_t szs_engine_fuzzy_scan_matches(szs_engine_s *engine, szs_scope_s *sco
                                           size_t text_length, size_t max_distance, size_t limit, size_t *counts, size_t *distances,
                                           size_t *ends, char const **error_message);
 
+/* ---- fuzzy scan occurrences (fuzzy_scan_occurrences.c) ------------------------------------------------------------------ */
+
+/** One end per occurrence of every query inside ONE text - the first column of every valley floor of the DP's bottom row that lies
+ *  within `max_distance`: `counts` of `queries->count` cells, `distances`, `starts` and `ends` dense `queries->count` x `limit`
+ *  matrices with the leftmost `limit` occurrences a row (`limit` 0: none is looked at; `starts` NULL: no reverse pass).  Unit-cost
+ *  byte Levenshtein engines only.  Uses the engine's rerank buffers. */
+sz_status_t szs_engine_fuzzy_scan_occurrences(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, void const *text,
+                                              size_t text_length, size_t max_distance, size_t limit, size_t *counts, size_t *distances,
+                                              size_t *starts, size_t *ends, char const **error_message);
+
 #endif /* SZS_INTERNAL_H_ */
