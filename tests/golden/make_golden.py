@@ -11,6 +11,8 @@ serial.hpp:677-689) compiled header-only from /root/reference by oracle/Makefile
 inputs (hex) next to the matrices the reference produced.  The GPU box has no /root/reference, so these committed
 vectors are what pins the oracle and the HIP path there.
 
+`fingerprint_ranges.json` has a generator of its own, next to the cases it stores: `python -m tests.fingerprint_range_cases --write`.
+
 `known_answers.json` is different: it is hand-transcribed from the reference's own tests (each entry cites its
 source line) and is NOT produced by running anything - it is what the reference's authors assert.
 """
