@@ -403,7 +403,7 @@ int szs_hip_levenshtein_fuzzy_matches_write(szs_rerank_side_t const *queries, ui
 
 /**
  *  ONE end per occurrence of every query inside that text, and where each starts (hip/myers_fuzzy_occurrences.hip;
- *  host/fuzzy_scan_occurrences.c).  An occurrence end of row r is a column j in [1, text_length] with
+ *  host/fuzzy_scan_matches.c).  An occurrence end of row r is a column j in [1, text_length] with
  *  D[m][j] <= `bound`, D[m][j] < D[m][j - 1] and (j == text_length or D[m][j] <= D[m][j + 1]).  COUNT and WRITE are the two launches
  *  above with "occurrence" in place of "hit": the same arguments, scratch, grid, refusals, flags and counters - a piece that is not
  *  the last walks one column more - and szs_hip_levenshtein_fuzzy_matches_offsets runs between them as it is.

@@ -1,8 +1,9 @@
 /*
  *  myers_fuzzy_scan.hip - the semi-global distance of every query inside ONE long text (szs_rocm_fuzzy_scan*, host/fuzzy_scan.c;
  *  DESIGN.md section 4.11): distance = min over j of D[m][j], end = the smallest j that attains it.  The distance, its table and a
- *  lane's walk are hip/fuzzy_core.hpp's, unchanged; rows, widths, flags and counters are hip/rerank_core.hpp's.  This file's own is
- *  the schedule: the text is cut into PIECES, the pieces are dealt to lanes, and the lanes' results are reduced exactly.
+ *  lane's walk are hip/fuzzy_core.hpp's; rows, widths, flags and counters are hip/rerank_core.hpp's; the piece a lane takes is
+ *  hip/fuzzy_pieces.hpp's matches_piece, the one the bounded scans take.  This file's own is the schedule: the text is cut into
+ *  PIECES, the pieces are dealt to lanes, and the lanes' results are reduced exactly.
  *
  *  - Piece p owns columns (p P, min(n, (p + 1) P)].  The lane that takes it walks from s = p P - warm, warm = min(p P, 2 m), so its
  *    DP has a free start at s instead of at 0: every value it sees is >= the true D[m][j] (fewer starts to choose from), and equal
@@ -22,7 +23,7 @@
  *  - The table is static LDS of the widest layout (8 KB), as hip/myers_fuzzy_tile.hip's.
  *  - Counters: cells and bytes as walked, warm-up included; one pair per row with a non-empty query, counted by chunk 0 alone.
  */
-#include "fuzzy_core.hpp"
+#include "fuzzy_pieces.hpp"
 
 namespace szs_hip {
 
@@ -40,19 +41,17 @@ __device__ __forceinline__ void fuzzy_scan_row(u32 *table, listed_row_t const &r
                                                u32 chunk, unsigned long long *__restrict__ keys, unsigned long long *counters) {
     fuzzy_table<words_, (int)wave_size_k>(table, row);
 
-    u64 const p = (u64)chunk * wave_size_k + threadIdx.x;
-    bool const live = row.has_row && row.query_length && p < pieces;
-    u64 const from = live ? p * piece : 0; // below text_length: pieces = ceil(text_length / piece)
-    u32 const warm = from < 2u * row.query_length ? (u32)from : 2u * row.query_length;
-    u32 const own = live ? (u32)(text_length - from < piece ? text_length - from : piece) : 0u;
-    u32 const first = (u32)from - warm, walked = own + warm; // first + walked <= text_length
+    matches_piece_t const lane = matches_piece(row.query_length, text_length, piece, pieces, chunk);
+    bool const live = row.has_row && row.query_length && lane.inside;
+    u32 const walked = live ? lane.walked : 0u;
 
     u32 best, match_end;
-    fuzzy_best_match<words_>(table, row.query_length, text + first, walked, live, best, match_end);
+    fuzzy_best_match<words_>(table, row.query_length, text + lane.first, walked, live, best, match_end);
 
-    u64 const key = wave_min_u64(live ? (u64)best << 32 | (first + match_end) : ~0ull);
+    u64 const key = wave_min_u64(live ? (u64)best << 32 | (lane.first + match_end) : ~0ull);
     if (threadIdx.x == 0 && key != ~0ull) atomicMin(&keys[row.row], (unsigned long long)key);
 
+    // (not matches_counted: this kernel also runs for a row without a query, which counts no pair and no bytes)
     listed_counters_t counted;
     if (live) counted.cells = (u64)row.query_length * walked, counted.bytes = walked;
     if (live && threadIdx.x == 0) counted.bytes += row.query_length, counted.pairs = chunk == 0; // the query: read once a workgroup

@@ -515,7 +515,7 @@ sz_status_t szs_rocm_fuzzy_scan_matches_u64tape(void *engine, szs_device_scope_t
     SZS_FUZZY_SCAN_MATCHES_BODY(input_from_u64tape)
 }
 
-/* ---- fuzzy scan occurrences (host/fuzzy_scan_occurrences.c) ----------------------------------------------------------- */
+/* ---- fuzzy scan occurrences (host/fuzzy_scan_matches.c) ----------------------------------------------------------- */
 
 #define SZS_FUZZY_SCAN_OCCURRENCES_BODY(MAKE_INPUT)                                                                                \
     szs_input_t query_input;                                                                                                       \

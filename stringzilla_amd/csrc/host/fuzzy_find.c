@@ -143,13 +143,7 @@ static sz_status_t fuzzy_find_call(szs_engine_s *engine, szs_scope_s *scope, szs
     hipError_t error = hipSuccess;
     for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block)
         status = szs_fuzzy_find_block(&call, q0, q_count - q0 < block ? q_count - q0 : block, &error, error_message);
-    hipError_t const drained = hipStreamSynchronize(listed->stream); /* synchronous, also when it fails */
-    if (status != sz_success_k) return status;
-    if (error == hipSuccess) error = drained;
-    if (error != hipSuccess) return szs_report_hip(error, error_message);
-    engine->last_profile = listed->total; /* the sums over the call; every other field blank */
-    engine->last_profile.host_milliseconds = szs_now_milliseconds() - started;
-    return szs_report(sz_success_k, error_message, NULL);
+    return szs_listed_close(listed, status, error, started, error_message);
 }
 
 sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,

@@ -19,7 +19,7 @@
 
 static char const fuzzy_scan_long_query[] = "A query of more than 256 bytes: beyond what fuzzy scan takes";
 
-/* (declared in rerank_internal.h: szs_rocm_fuzzy_scan_matches* - fuzzy_scan_matches.c - cuts its text by the same rule) */
+/* (declared in rerank_internal.h: the bounded scans - fuzzy_scan_matches.c - cut their text by the same rule) */
 fuzzy_scan_cut_t fuzzy_scan_cut(size_t rows, uint64_t n) {
     uint64_t const wanted = (uint64_t)SZS_FUZZY_SCAN_WAVES * SZS_FUZZY_SCAN_FILLS;
     uint64_t const chunks_wanted = (wanted + rows - 1) / rows, lanes_wanted = chunks_wanted * SZS_FUZZY_SCAN_LANES;
@@ -164,13 +164,7 @@ static sz_status_t fuzzy_scan_call(szs_engine_s *engine, szs_scope_s *scope, szs
 
     for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block)
         status = fuzzy_scan_block(&scan, q0, q_count - q0 < block ? q_count - q0 : block, &error, error_message);
-    hipError_t const drained = hipStreamSynchronize(listed->stream); /* synchronous, also when it fails */
-    if (status != sz_success_k) return status;
-    if (error == hipSuccess) error = drained;
-    if (error != hipSuccess) return szs_report_hip(error, error_message);
-    engine->last_profile = listed->total; /* the sums over the call; every other field blank */
-    engine->last_profile.host_milliseconds = szs_now_milliseconds() - started;
-    return szs_report(sz_success_k, error_message, NULL);
+    return szs_listed_close(listed, status, error, started, error_message);
 }
 
 sz_status_t szs_engine_fuzzy_scan(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, void const *text, size_t text_length,

@@ -218,3 +218,13 @@ sz_status_t szs_listed_block_finish(szs_listed_call_t *call, hipError_t error, h
     if (longest > total->longest_query) total->longest_query = longest;
     return sz_success_k;
 }
+
+sz_status_t szs_listed_close(szs_listed_call_t *call, sz_status_t status, hipError_t error, double started, char const **error_message) {
+    hipError_t const drained = hipStreamSynchronize(call->stream); /* synchronous, also when it fails */
+    if (status != sz_success_k) return status;
+    if (error == hipSuccess) error = drained;
+    if (error != hipSuccess) return szs_report_hip(error, error_message);
+    call->engine->last_profile = call->total; /* the sums over the call; every other field blank */
+    call->engine->last_profile.host_milliseconds = szs_now_milliseconds() - started;
+    return szs_report(sz_success_k, error_message, NULL);
+}

@@ -88,6 +88,11 @@ hipError_t szs_listed_block_end(szs_listed_call_t *call, hipError_t error);
 sz_status_t szs_listed_block_finish(szs_listed_call_t *call, hipError_t error, hipError_t *hip_error, unsigned launches, uint32_t longest,
                                     size_t bytes_per_pair, sz_status_t unfit_status, char const *unfit_message, char const **error_message);
 
+/** The end of a call whose profile is `call->total` as it stands, behind its loop over the blocks: drains the stream - synchronous,
+ *  also when the call fails - and reports `status` where a block failed (its message is set), else the HIP `error` of the blocks or of
+ *  the drain; on success the engine's last profile becomes the sums over the call with the host time since `started`. */
+sz_status_t szs_listed_close(szs_listed_call_t *call, sz_status_t status, hipError_t error, double started, char const **error_message);
+
 /* ---- fuzzy find's own steps (fuzzy_find.c), which the search (fuzzy_search.c) runs on the rows it has found ---------------------- */
 
 /** What the blocks of one fuzzy-find call share. */
@@ -108,7 +113,7 @@ sz_status_t szs_fuzzy_find_prepare(szs_fuzzy_find_call_t *call, szs_input_t cons
  *  hip/myers_fuzzy_spans.hip behind it; drains the stream and adds the block to `listed.total`. */
 sz_status_t szs_fuzzy_find_block(szs_fuzzy_find_call_t *call, size_t q0, size_t rows, hipError_t *hip_error, char const **error_message);
 
-/* ---- fuzzy scan's cut (fuzzy_scan.c), which fuzzy scan matches (fuzzy_scan_matches.c) shares -------------------------------------- */
+/* ---- fuzzy scan's cut (fuzzy_scan.c), which the bounded scans (fuzzy_scan_matches.c) share ---------------------------------------- */
 
 /** How a text of `n` bytes is cut for a block of `rows` rows: the bytes of a piece, the pieces, and the chunks of 64 pieces - the
  *  workgroups of a row.  Both constants are choices, not measurements. */
@@ -117,19 +122,6 @@ typedef struct {
 } fuzzy_scan_cut_t;
 
 fuzzy_scan_cut_t fuzzy_scan_cut(size_t rows, uint64_t n);
-
-/* ---- the blocks and the scratch of fuzzy scan matches (fuzzy_scan_matches.c), which fuzzy scan occurrences (fuzzy_scan_occurrences.c)
- *      shares --------------------------------------------------------------------------------------------------------------------- */
-
-#define SZS_FUZZY_MATCHES_MOST_LIMIT ((size_t)1 << 24)          /* a choice, not a measurement: one row of outputs is then 256 MiB */
-#define SZS_FUZZY_MATCHES_SCRATCH_BYTES ((uint64_t)256 << 20)   /* a block's piece and chunk counts; a choice, not a measurement */
-#define SZS_FUZZY_MATCHES_MOST_WORKGROUPS ((uint64_t)0x7FFFFFFF) /* the grid of a launch */
-#define SZS_FUZZY_MATCHES_LANES 64u                              /* the pieces of a chunk */
-
-/** The bytes of a block's scratch - 64 piece counts and one chunk count per (row, chunk) - a multiple of 16. */
-uint64_t fuzzy_matches_scratch(uint64_t rows, uint64_t chunks);
-/** The rows of a block with `limit` slots a row, at least one, and the cut of a text of `n` bytes for them. */
-size_t fuzzy_matches_block_rows(size_t q_count, size_t limit, int within_stage_budget, uint64_t n, fuzzy_scan_cut_t *cut);
 
 /**
  *  The rows of a block whose query has at most SZS_RERANK_LONGEST_QUERY bytes into `order`, longest query first (a counting sort of

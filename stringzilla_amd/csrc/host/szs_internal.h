@@ -439,7 +439,7 @@ sz_status_t szs_engine_fuzzy_scan_matches(szs_engine_s *engine, szs_scope_s *sco
                                           size_t text_length, size_t max_distance, size_t limit, size_t *counts, size_t *distances,
                                           size_t *ends, char const **error_message);
 
-/* ---- fuzzy scan occurrences (fuzzy_scan_occurrences.c) ------------------------------------------------------------------ */
+/* ---- fuzzy scan occurrences (fuzzy_scan_matches.c) ------------------------------------------------------------------ */
 
 /** One end per occurrence of every query inside ONE text - the first column of every valley floor of the DP's bottom row that lies
  *  within `max_distance`: `counts` of `queries->count` cells, `distances`, `starts` and `ends` dense `queries->count` x `limit`

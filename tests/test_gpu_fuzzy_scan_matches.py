@@ -304,6 +304,123 @@ def test_outputs_and_memory_kinds(gpu, engine, piece, planted):
     assert same(engine.fuzzy_scan_matches(queries, text, 2, limit=limit, device=gpu), want)  # and the call afterwards
 
 
+class TwoBlocks:
+    """What makes the scratch cap cut a call in two, and its oracle.  At a piece of 64 a text of 2^20 bytes has 256 chunks, a row's
+    scratch is 256 x 65 x 4 = 66,560 bytes and a block floor(2^28 / 66,560) = 4,032 rows: 4,037 queries leave 5 for a second block.
+    The queries cycle through 37 patterns of 4 to 8 bytes over ACGT; 4,032 mod 37 = 36, so rows r and r - 4,032 never hold the same
+    pattern - the last five hold patterns 36, 0, 1, 2 and 3.  The text is the filler byte `x` but for two windows of 2,000 bytes with
+    copies under 0 or 1 edits: one across column 4096 - a chunk boundary - and one that ends 30 bytes before the text does.  On filler
+    the DP's column is 0 ... m again after m bytes and m > the bound, so the hits of the text are those of the windows, shifted:
+    `windows` holds (offset, patterns' last rows over the window's bytes)."""
+    ROWS, BLOCK, PATTERNS, N, PIECE, BOUND, LIMIT, EDGE = 4037, 4032, 37, 1 << 20, 64, 1, 4, 8
+
+    def __init__(self):
+        rng = random.Random(1812)
+        alphabet = b"ACGT"
+        once = [2, 5, 36]  # of the last five rows' patterns 36 and 2 are planted once a window, 0 and 3 often, 1 nowhere
+        often = [p for p in range(self.PATTERNS) if p % 3 == 0 and p not in once]
+        self.patterns = []
+        while len(self.patterns) < self.PATTERNS:  # (8 bytes where a count is to stay small: no other copy comes within the bound)
+            length = 8 if len(self.patterns) in once + [1] else rng.randint(4, 8)
+            pattern = bytes(rng.choice(alphabet) for _ in range(length))
+            if pattern not in self.patterns:
+                self.patterns.append(pattern)
+        self.queries = [self.patterns[r % self.PATTERNS] for r in range(self.ROWS)]
+        text = bytearray(b"x" * self.N)
+        self.windows = []
+        for offset in (4096 - 1000, self.N - 30 - 2000):
+            at, end = offset + 2 * self.EDGE, offset + 2000 - 2 * self.EDGE
+            for p in once:  # one copy, its first byte replaced by filler: one hit at distance 1, fewer than the limit in all
+                text[at:at + len(self.patterns[p])] = b"x" + self.patterns[p][1:]
+                at += len(self.patterns[p]) + 11
+            while at + 10 < end:
+                copy = _mutated(rng, self.patterns[rng.choice(often)], alphabet, rng.randint(0, 1))
+                text[at:at + len(copy)] = copy
+                at += len(copy) + rng.randint(3, 11)
+            window = bytes(text[offset:offset + 2000])
+            assert window[:self.EDGE] == window[-self.EDGE:] == b"x" * self.EDGE
+            self.windows.append((offset, window, last_rows(self.patterns, window)))
+        assert text[4090:4102].count(b"x") < 12  # planted bytes on both sides of the chunk boundary
+        self.text = bytes(text)
+
+    def per_row(self, per_pattern):
+        """Rows of (ends, distances, ...) per pattern, each ascending in the text, as the call's (counts, matrices ...) per query: the
+        leftmost LIMIT of every row."""
+        width = len(per_pattern[0])
+        counts = np.array([len(per_pattern[r % self.PATTERNS][0]) for r in range(self.ROWS)], np.uint64)
+        matrices = [np.full((self.ROWS, self.LIMIT), EMPTY, np.uint64) for _ in range(width)]
+        for r in range(self.ROWS):
+            for matrix, values in zip(matrices, per_pattern[r % self.PATTERNS]):
+                matrix[r, :min(len(values), self.LIMIT)] = values[:self.LIMIT]
+        # what the oracle must hold: rows above, below and without the limit in both blocks, and a second block that differs from
+        # what the first block's rows - a wrong first row - would give
+        for rows in (slice(0, self.BLOCK), slice(self.BLOCK, self.ROWS)):
+            assert (counts[rows] > self.LIMIT).any() and (counts[rows] == 0).any() and ((counts[rows] > 0) & (counts[rows] < self.LIMIT)).any()
+        assert all(not np.array_equal(matrices[-1][self.BLOCK + r], matrices[-1][r]) for r in range(self.ROWS - self.BLOCK))  # the ends
+        return (counts, *matrices)
+
+    def expected(self):
+        """(counts, distances, ends) of fuzzy scan matches."""
+        per_pattern = []
+        for p in range(self.PATTERNS):
+            ends, distances = [], []
+            for offset, window, last in self.windows:
+                hits = np.flatnonzero(last[p, 1:] <= self.BOUND) + 1
+                assert not len(hits) or (self.EDGE < hits[0] and hits[-1] <= len(window) - self.EDGE)  # what makes the windows exact
+                ends.append(hits + offset), distances.append(last[p, hits])
+            per_pattern.append((np.concatenate(distances).astype(np.uint64), np.concatenate(ends).astype(np.uint64)))
+        return self.per_row(per_pattern)
+
+
+@pytest.fixture(scope="module")
+def two_blocks():
+    return TwoBlocks()
+
+
+def on_device_outputs(rows, limit, matrices):
+    import torch
+
+    return (torch.full((rows,), 7, dtype=torch.int64).cuda(),) + tuple(torch.full((rows, limit), 7, dtype=torch.int64).cuda() for _ in range(matrices))
+
+
+def test_two_blocks_through_the_scratch_cap(gpu, engine, piece, two_blocks):
+    """Outputs in device memory, written where they are: the second block's rows, queries and scratch begin where the first's end."""
+    import torch
+
+    case = two_blocks
+    piece(case.PIECE)
+    assert _abi.fuzzy_scan_probe(case.ROWS, 8, case.N)[:2] == (case.PIECE, case.N // case.PIECE)
+    want = case.expected()
+    on_device = torch.frombuffer(bytearray(case.text), dtype=torch.uint8).cuda()
+    out = on_device_outputs(case.ROWS, case.LIMIT, 2)
+    assert engine.fuzzy_scan_matches(case.queries, on_device, case.BOUND, limit=case.LIMIT, device=gpu, out=out) is out
+    assert engine.last_call_profile().launches == 2 * 3
+    got = [array.cpu().numpy().view(np.uint64) for array in out]
+    assert np.array_equal(got[0], want[0]), np.flatnonzero(got[0] != want[0])[:8]
+    assert same(got, want), [np.argwhere(g != w)[:4] for g, w in zip(got, want)]  # every filled slot, and all ones behind them
+    for matrix in got[1:]:
+        assert all((matrix[r, int(count):] == EMPTY).all() for r, count in enumerate(want[0]) if count < case.LIMIT)
+
+
+def test_two_blocks_through_the_staging_budget(gpu, engine, piece, planted):
+    """Outputs in plain host memory: with 2^17 slots a row a staged block is 128 MiB / (2^17 x 8) = 128 rows, and 130 queries leave 2
+    for a second one.  128 mod 11 = 7: rows r and r - 128 never hold the same query."""
+    queries, text, last = planted
+    rows, limit = 130, 1 << 17
+    queries, last = [queries[r % len(queries)] for r in range(rows)], last[[r % len(queries) for r in range(rows)]]
+    piece(64)
+    counts, distances, ends = expected(queries, last, 1, N)
+    most = int(counts.max())
+    assert 0 < most < limit and counts[128] != counts[0] and counts[129] != counts[1]
+    got = (np.full(rows, UNTOUCHED, np.uint64), np.full((rows, limit), UNTOUCHED, np.uint64), np.full((rows, limit), UNTOUCHED, np.uint64))
+    assert engine.fuzzy_scan_matches(queries, text, 1, limit=limit, device=gpu, out=got) is got
+    assert engine.last_call_profile().launches == 2 * 3
+    assert np.array_equal(got[0], counts), np.flatnonzero(got[0] != counts)[:8]
+    for matrix, want in zip(got[1:], (distances, ends)):
+        assert np.array_equal(matrix[:, :most], want[:, :most]), np.argwhere(matrix[:, :most] != want[:, :most])[:4]
+        assert (matrix[:, most:] == EMPTY).all()
+
+
 def test_determinism_and_the_profile(gpu, engine, piece, planted):
     queries, text, last = planted
     filled = sum(1 for query in queries if query)

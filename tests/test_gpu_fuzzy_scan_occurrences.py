@@ -11,7 +11,8 @@ import pytest
 
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
-from test_gpu_fuzzy_scan_matches import EMPTY, N, PIECES, QUERY_LENGTHS, UNTOUCHED, _last_rows, _mutated, last_rows, same
+from test_gpu_fuzzy_scan_matches import (EMPTY, N, PIECES, QUERY_LENGTHS, UNTOUCHED, TwoBlocks, _last_rows, _mutated, last_rows,
+                                         on_device_outputs, same)
 
 pytestmark = pytest.mark.gpu
 
@@ -342,6 +343,66 @@ def test_outputs_and_memory_kinds(gpu, engine, piece, planted):
     assert refused.value.status_name == "unexpected_dimensions" and "256" in str(refused.value)
     assert all((array == UNTOUCHED).all() for array in out)
     assert same(engine.fuzzy_scan_occurrences(queries, text, 2, limit=limit, device=gpu), want)  # and the call afterwards
+
+
+@pytest.fixture(scope="module")
+def two_blocks():
+    """tests/test_gpu_fuzzy_scan_matches.py's case with (counts, distances, starts, ends) of the occurrences: the rule and the reverse
+    DP over each window, shifted by the window's offset."""
+    case = TwoBlocks()
+    per_pattern = []
+    for p, pattern in enumerate(case.patterns):
+        ends, distances, starts = [], [], []
+        for offset, window, last in case.windows:
+            hits = np.flatnonzero(last[p, 1:] <= case.BOUND) + 1
+            assert not len(hits) or (case.EDGE < hits[0] and hits[-1] <= len(window) - case.EDGE)  # what makes the windows exact
+            found = occurrence_ends(last[p], case.BOUND)
+            begins = starts_of(pattern, window, found, last[p, found])
+            ends.append(found + offset), distances.append(last[p, found]), starts.append(begins.astype(np.int64) + offset)
+        per_pattern.append(tuple(np.concatenate(column).astype(np.uint64) for column in (distances, starts, ends)))
+    return case, case.per_row(per_pattern)
+
+
+@pytest.mark.parametrize("starts", [True, False], ids=["starts", "no-starts"])
+def test_two_blocks_through_the_scratch_cap(gpu, engine, piece, two_blocks, starts):
+    """Outputs in device memory, written where they are: the second block's rows, queries and scratch begin where the first's end."""
+    import torch
+
+    case, want = two_blocks
+    piece(case.PIECE)
+    assert _abi.fuzzy_scan_probe(case.ROWS, 8, case.N)[:2] == (case.PIECE, case.N // case.PIECE)
+    if not starts:
+        want = (want[0], want[1], want[3])
+    on_device = torch.frombuffer(bytearray(case.text), dtype=torch.uint8).cuda()
+    out = on_device_outputs(case.ROWS, case.LIMIT, len(want) - 1)
+    assert engine.fuzzy_scan_occurrences(case.queries, on_device, case.BOUND, limit=case.LIMIT, starts=starts, device=gpu, out=out) is out
+    assert engine.last_call_profile().launches == 2 * (4 if starts else 3)
+    got = [array.cpu().numpy().view(np.uint64) for array in out]
+    assert np.array_equal(got[0], want[0]), np.flatnonzero(got[0] != want[0])[:8]
+    assert same(got, want), [np.argwhere(g != w)[:4] for g, w in zip(got, want)]  # every filled slot, and all ones behind them
+    for matrix in got[1:]:
+        assert all((matrix[r, int(count):] == EMPTY).all() for r, count in enumerate(want[0]) if count < case.LIMIT)
+
+
+@pytest.mark.parametrize("starts", [True, False], ids=["starts", "no-starts"])
+def test_two_blocks_through_the_staging_budget(gpu, engine, piece, planted, starts):
+    """Outputs in plain host memory: with 2^17 slots a row a staged block is 128 MiB / (2^17 x 8) = 128 rows, and 130 queries leave 2
+    for a second one.  128 mod 11 = 7: rows r and r - 128 never hold the same query."""
+    rows, limit = 130, 1 << 17
+    piece(64)
+    want = planted.expected(1, N, starts=starts)
+    want = [array[[r % len(planted.queries) for r in range(rows)]] for array in want]
+    counts = want[0]
+    most = int(counts.max())
+    assert 0 < most < limit and counts[128] != counts[0] and counts[129] != counts[1]
+    queries = [planted.queries[r % len(planted.queries)] for r in range(rows)]
+    got = (np.full(rows, UNTOUCHED, np.uint64),) + tuple(np.full((rows, limit), UNTOUCHED, np.uint64) for _ in want[1:])
+    assert engine.fuzzy_scan_occurrences(queries, planted.text, 1, limit=limit, starts=starts, device=gpu, out=got) is got
+    assert engine.last_call_profile().launches == 2 * (4 if starts else 3)
+    assert np.array_equal(got[0], counts), np.flatnonzero(got[0] != counts)[:8]
+    for matrix, wanted in zip(got[1:], want[1:]):
+        assert np.array_equal(matrix[:, :most], wanted[:, :most]), np.argwhere(matrix[:, :most] != wanted[:, :most])[:4]
+        assert (matrix[:, most:] == EMPTY).all()
 
 
 def test_determinism_and_the_profile(gpu, engine, piece, planted):
