@@ -65,7 +65,7 @@ def opcode_of(line):
     return token
 
 
-def main_loop(body, prefer_dpp=False):
+def main_loop(body, prefer_dpp=False, prefer_carry=False):
     """Blocks -> innermost loop header; returns (header label, Counter of VALU opcodes) of the loop with the most VALU."""
     loops, header_of_block, block = defaultdict(Counter), None, None
     for line in body:
@@ -90,7 +90,11 @@ def main_loop(body, prefer_dpp=False):
     # checks: the main loop is the largest one that hands values over by DPP and compares next to nothing)
     stepping = {name: mix for name, mix in loops.items() if any(opcode.endswith("_dpp") for opcode in mix) and
                 sum(count for opcode, count in mix.items() if opcode.startswith("v_cmp")) <= 4} if prefer_dpp else {}
-    pool = stepping or loops
+    # The launch that plans itself holds the sorters too, and the loop in which the query side's sorter weighs the pairing rules
+    # (pair_rule.h: maxima, selects and popcounts, no column) is larger than any column loop since the column lost a shift: its
+    # main loop is the largest one that holds links of the carry chain.
+    chained = {name: mix for name, mix in loops.items() if mix["v_addc_co_u32"]} if prefer_carry else {}
+    pool = stepping or chained or loops
     header = max(pool, key=lambda name: sum(pool[name].values()))
     return header, pool[header]
 
@@ -104,7 +108,7 @@ def main():
         for mangled, body in kernels_of(source):
             pretty = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip()
             short = pretty.split("(")[0].replace("void ", "").replace("szs_hip::", "").strip()
-            header, mix = main_loop(body, prefer_dpp="weighted_team_kernel" in pretty)
+            header, mix = main_loop(body, prefer_dpp="weighted_team_kernel" in pretty, prefer_carry="myers_short_fused_kernel" in pretty)
             total = sum(mix.values())
             if not total:
                 continue

@@ -97,24 +97,29 @@ __global__ __launch_bounds__(256) void k_lds_b128(uint32_t *out, uint32_t seed, 
 
 
 /* The Myers column update of csrc/hip/lev_myers.hip on synthetic match masks held in registers: the pure-VALU rate of
- * the real instruction mix (bitop3 / or / and / addc carry chain / alignbit), no LDS, no memory. */
+ * the real instruction mix (bitop3 / or / and / addc carry chain / ONE alignbit: HN << 1 is the adder's carries, hip/myers_core.hpp),
+ * no LDS, no memory. */
+template <int table_>
+__device__ __forceinline__ uint32_t bitop3_probe(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "v"(a), "v"(b), "v"(c), "n"(table_));
+    return r;
+}
 template <int words_>
 __device__ __forceinline__ void myers_column_probe(uint32_t (&vp)[words_], uint32_t (&vn)[words_], uint32_t const (&eq)[words_],
                                                    uint32_t &hp_history, uint32_t &hn_history) {
-    uint32_t carry = 0, hp_below = 0, hn_below = 0;
+    uint32_t carry = 0, hp_below = 0;
 #pragma unroll
     for (int w = 0; w < words_; ++w) {
-        uint32_t const xv = eq[w] | vn[w];
+        uint32_t const xv = eq[w] | vn[w], kept = eq[w] | vp[w];
         uint32_t carry_out;
         uint32_t const sum = __builtin_addc(eq[w] & vp[w], vp[w], carry, &carry_out);
         carry = carry_out;
-        uint32_t const d0 = (sum ^ vp[w]) | eq[w];
-        uint32_t const hp = vn[w] | ~(d0 | vp[w]);
-        uint32_t const hn = vp[w] & d0;
+        uint32_t const hn_shifted = bitop3_probe<0x96>(sum, kept, eq[w]); /* sum ^ K ^ Eq: the carries into every bit */
+        uint32_t const hp = bitop3_probe<0xf1>(vn[w], sum, kept);         /* VN | ~(sum | K) */
         uint32_t const hp_shifted = w == 0 ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
-        uint32_t const hn_shifted = w == 0 ? (hn << 1) : __builtin_amdgcn_alignbit(hn, hn_below, 31);
-        hp_below = hp, hn_below = hn;
-        vp[w] = hn_shifted | ~(xv | hp_shifted);
+        hp_below = hp;
+        vp[w] = bitop3_probe<0xf1>(hn_shifted, xv, hp_shifted);           /* HNs | ~(X | HPs) */
         vn[w] = hp_shifted & xv;
     }
     (void)hp_history, (void)hn_history; /* the kernel no longer tracks the score per column (popcount at text end) */
@@ -159,6 +164,8 @@ __global__ __launch_bounds__(256) void k_myers_block(uint32_t *out, uint32_t see
     if (sum == 0x12345678u) out[0] = sum;
 }
 
+/* (One vector per lane, as in the kernels.  Two and four independent vectors per lane, their columns interleaved, and 2 ... 8
+ * workgroups a CU were measured too - profiles/r19/README.md: the rate of a width does not move with either.) */
 template <int words_>
 __global__ __launch_bounds__(256) void k_myers_pure(uint32_t *out, uint32_t seed, int iterations) {
     uint32_t vp[words_], vn[words_], eq[4][words_];
@@ -281,10 +288,24 @@ int main() {
     {   /* word-steps per second: one word-step = 32 DP cells of one lane */
         int const columns = 1600; /* iterations x 16 */
         double const base = (double)blocks * 256 * columns;
-        printf(", \"myers_pure_W4_Tcells\": %.2f", base * 128 / time_kernel(k_myers_pure<4>, out, columns / 16, blocks) / 1e12);
-        printf(", \"myers_pure_W5_Tcells\": %.2f", base * 160 / time_kernel(k_myers_pure<5>, out, columns / 16, blocks) / 1e12);
-        printf(", \"myers_pure_W8_Tcells\": %.2f", base * 256 / time_kernel(k_myers_pure<8>, out, columns / 16, blocks) / 1e12);
-        printf(", \"myers_pure_W1_Tcells\": %.2f", base * 32 / time_kernel(k_myers_pure<1>, out, columns / 16, blocks) / 1e12);
+        /* `myers_pure_W4_Tcells` is the key bench.py prices config 2's launch against.  With both shifts the column's rate did not
+         * depend on the width (125.7 T at 4 words, 125.9 at 8) and the 4-word kernel stood for all of them; with one shift it does
+         * (4 words 132 ... 138 T, 8 152 ... 157, 10 146 ... 150, at the same 9.1 ... 9.3 instructions per word-step; why is not
+         * understood), and config 2's vectors are pairs of 8 to 10 words, which run above the 4-word figure (147 T) - and level
+         * with this probe's own 10-word figure, so a width's rate here is NOT a proven bound for the kernel at that width.  The
+         * key holds the fastest width measured here and says which; the 4-word rate stays under a name of its own. */
+        double const four = base * 128 / time_kernel(k_myers_pure<4>, out, columns / 16, blocks) / 1e12;
+        double const five = base * 160 / time_kernel(k_myers_pure<5>, out, columns / 16, blocks) / 1e12;
+        double const eight = base * 256 / time_kernel(k_myers_pure<8>, out, columns / 16, blocks) / 1e12;
+        double const ten = base * 320 / time_kernel(k_myers_pure<10>, out, columns / 16, blocks) / 1e12;
+        double const one = base * 32 / time_kernel(k_myers_pure<1>, out, columns / 16, blocks) / 1e12;
+        double const widths[] = {four, five, eight, ten};
+        int const words_of[] = {4, 5, 8, 10};
+        int fastest = 0;
+        for (int i = 1; i < 4; ++i) fastest = widths[i] > widths[fastest] ? i : fastest;
+        printf(", \"myers_pure_W4_Tcells\": %.2f, \"myers_pure_W4_Tcells_is_the_rate_at_words\": %d", widths[fastest], words_of[fastest]);
+        printf(", \"myers_pure_4_words_Tcells\": %.2f, \"myers_pure_W5_Tcells\": %.2f, \"myers_pure_W8_Tcells\": %.2f", four, five, eight);
+        printf(", \"myers_pure_W10_Tcells\": %.2f, \"myers_pure_W1_Tcells\": %.2f", ten, one);
         printf(", \"myers_block_W4_Tcells\": %.2f", base * 128 / time_kernel((k_myers_block<4, false>), out, columns / 16, blocks) / 1e12);
         printf(", \"myers_block_addshift_W4_Tcells\": %.2f", base * 128 / time_kernel((k_myers_block<4, true>), out, columns / 16, blocks) / 1e12);
         printf(", \"myers_block_W8_Tcells\": %.2f", base * 256 / time_kernel((k_myers_block<8, false>), out, columns / 16, blocks) / 1e12);

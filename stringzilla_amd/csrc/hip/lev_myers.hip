@@ -109,7 +109,14 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
     u32 const second_row = pad + first_length + 2u;                                    // a pair: the second query's first row
 
     // ---- Peq: zero, then scatter the pattern's bits (LDS atomics; a 128-symbol query is 128 ORs per workgroup).
-    for (int i = threadIdx.x; i < layout::total_dwords; i += 256) peq[i] = 0;
+    //      A pair: every row holds the lower separator row s0 instead (myers_column; the scatter ORs, so the bit stays).
+    if constexpr (paired_) {
+        u32 const s0_dword = (second_row - 2u) >> 5, s0_mask = 1u << ((second_row - 2u) & 31u);
+        for (int i = threadIdx.x; i < layout::total_dwords; i += 256) // [chunk][row][word in chunk]: dword i is word ...
+            peq[i] = (u32)(i / (rows * layout::chunk_words) * layout::chunk_words + i % layout::chunk_words) == s0_dword ? s0_mask : 0u;
+    }
+    else
+        for (int i = threadIdx.x; i < layout::total_dwords; i += 256) peq[i] = 0;
     if constexpr (runes_) {
         if (alphabet) { // a renumbered batch (utf8.hip): `keys` is a direct table, id -> Peq row (0: not in the pattern)
             for (u32 i = threadIdx.x; i <= alphabet; i += 256) keys[i] = 0;
@@ -160,13 +167,13 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
         }
     }
     __syncthreads();
-    // (a pair: the separator rows s0, s1 and the first query's top row, per word - uniform, so scalar registers)
+    // (a pair: the separator rows s0 and s1, and s0 alone, per word - uniform, copied to vector registers once per workgroup)
     pattern_pair_t<words_> boundary;
     if constexpr (paired_) {
 #pragma unroll
         for (int w = 0; w < words_; ++w) {
             boundary.separators[w] = bits_in_word(second_row - 2u, second_row, w);
-            boundary.tops[w] = first_length ? bits_in_word(second_row - 3u, second_row - 2u, w) : 0u;
+            boundary.lower[w] = bits_in_word(second_row - 2u, second_row - 1u, w);
         }
     }
 

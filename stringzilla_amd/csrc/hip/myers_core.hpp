@@ -78,50 +78,72 @@ __device__ __forceinline__ bool ref_is_current(szs_ref_guard_t const &guard, int
 }
 
 /** No query boundary inside the bit-vector: the column of a single pattern (every mask below folds to nothing). */
-struct single_pattern_t {
-    __device__ static constexpr u32 separator(int) { return 0; }
-    __device__ static constexpr u32 top(int) { return 0; }
-};
+struct single_pattern_t {};
 
 /** Two patterns in one bit-vector (pad, q1, separator rows s0 s1, q2 from bit 0 up): per-word masks, uniform over the
- *  workgroup (they live in SGPRs).  `separators` marks s0 and s1, `tops` q1's last row.  See myers_column. */
+ *  workgroup, held in one VGPR each (the operands of the column's v_bitop3s).  `separators` marks s0 and s1, `lower` s0 alone -
+ *  the bit that EVERY row of a paired match-mask table holds.  See myers_column. */
 template <int words_>
 struct pattern_pair_t {
-    u32 separators[words_], tops[words_];
-    __device__ u32 separator(int w) const { return separators[w]; }
-    __device__ u32 top(int w) const { return tops[w]; }
+    u32 separators[words_], lower[words_];
 };
+
+/** r = f(a, b, c) bit by bit in ONE full-rate v_bitop3_b32; bit ((a << 2) | (b << 1) | c) of `table_` is f(a, b, c), i.e. the
+ *  same expression over a = 0xF0, b = 0xCC, c = 0xAA.  Spelled out because LLVM, given the C expression, splits some of the
+ *  column's functions in two or shares a subterm with a neighbour at the price of a v_or per word-step. */
+template <int table_>
+__device__ __forceinline__ u32 bitop3(u32 a, u32 b, u32 c) {
+    u32 r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(r) : "v"(a), "v"(b), "v"(c), "n"(table_));
+    return r;
+}
 
 /** One column of the DP matrix: consumes the match masks of one text byte and updates the vertical delta vectors.
  *
- *  With two patterns in the vector (pattern_pair_t) the separator rows carry no Peq bits and start with VP = VN = 0; three
- *  substitutions keep them so, and cost no instruction (each is the third operand of a v_bitop3):
- *    X~ = Eq | VN | Msep replaces X in VP' / VN' (the sum and D0 keep plain Eq); HN = VP & D0 & ~Mtop; VN' = HPs & X~ & ~Msep.
- *  s0 then swallows whatever q1's top row hands up, the add's carry dies in it (VP = 0 there), and s1 - D0 = 0 - gives q2's
- *  first row HPs = 1, HNs = 0 and carry 0: exactly DP row zero, as bit 0 of the vector gets it. */
-template <int words_, typename boundary_t = single_pattern_t, bool materialise_ = true>
+ *  Hyyro's column is  D0 = (((Eq & VP) + VP) ^ VP) | Eq,  HP = VN | ~(D0 | VP),  HN = VP & D0,  VP' = HN << 1 | ~(X | HP << 1),
+ *  VN' = HP << 1 & X  with X = Eq | VN.  HN << 1 is never shifted here, because the adder has it already: the carry OUT of bit i
+ *  of `sum = (Eq & VP) + VP` is maj(Eq_i & VP_i, VP_i, c_i) = VP_i & (Eq_i | c_i), and since VP & VN = 0 that is HN_i = VP_i & D0_i.
+ *  So HN << 1 is the vector of carries INTO each bit, sum ^ (Eq & VP) ^ VP - across words too: bit 0 of word w takes the addc's
+ *  carry.  With K = Eq | VP, computed before the add:
+ *      HNs = sum ^ K ^ Eq            HP = VN | ~(sum | K)     (D0 | VP == sum | K: D0 itself is not needed)
+ *  Per word-step: 7 full-rate logic ops (Eq & VP, K, X, HNs, HP, VP', VN'), the addc and ONE v_alignbit (HP << 1) - 9.5 VALU
+ *  with what surrounds them, two of them half-rate where the older column (both shifts) had three.
+ *
+ *  With two patterns in the vector (pattern_pair_t) the separator rows start with VP = VN = 0 and stay so, at no instruction:
+ *  every mask is the third operand of a v_bitop3.  X~ = Eq | VN | Msep replaces X; VN' = HPs & X~ & ~Msep; and every Peq row
+ *  holds the s0 bit, which K* = (Eq | VP) & ~Ms0 drops again: `Eq = 1, K* = 0` then happens at s0 and nowhere else (Eq is part
+ *  of K on every other row), and HNs = (sum ^ K* ^ Eq) & ~(Eq & ~K*) is 0 there - q1's top row hands its carry to nobody.
+ *  The sum never sees the bit (Eq & VP, VP = 0 at s0): s0 swallows the carry, s1 sees none and - sum = K* = 0 - gives q2's
+ *  first row HPs = 1, HNs = 0: exactly DP row zero, as bit 0 of the vector gets it. */
+template <int words_, typename boundary_t = single_pattern_t, bool materialise_ = true, bool spelled_carries_ = true>
 __device__ __forceinline__ void myers_column(u32 (&vp)[words_], u32 (&vn)[words_], u32 const (&eq)[words_],
                                              boundary_t const &boundary = {}) {
-    u32 carry = 0, hp_below = 0, hn_below = 0;
+    constexpr bool paired = !std::is_same<boundary_t, single_pattern_t>::value;
+    static_assert(spelled_carries_ || !paired, "a pair's HNs is not a function the compiler finds by itself");
+    u32 carry = 0, hp_below = 0;
 #pragma unroll
     for (int w = 0; w < words_; ++w) {
-        u32 xv = eq[w] | vn[w];
-        // (a pair: X~ is ONE full-rate v_bitop3 - left to itself LLVM keeps X for VN' and spends a v_or on X | Msep for VP',
-        // or picks the half-rate v_or3_b32)
-        if constexpr (!std::is_same<boundary_t, single_pattern_t>::value)
-            asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe" : "=v"(xv) : "v"(eq[w]), "v"(vn[w]), "v"(boundary.separator(w)));
+        u32 xv, kept, hn_shifted;
+        if constexpr (paired) {
+            xv = bitop3<0xfe>(eq[w], vn[w], boundary.separators[w]);   // Eq | VN | Msep
+            kept = bitop3<0x54>(eq[w], vp[w], boundary.lower[w]);      // (Eq | VP) & ~Ms0
+        }
+        else
+            xv = eq[w] | vn[w], kept = eq[w] | vp[w];
         u32 carry_out;
         u32 const sum = __builtin_addc(eq[w] & vp[w], vp[w], carry, &carry_out); // one link of the W-word carry chain
         carry = carry_out;
-        u32 const d0 = (sum ^ vp[w]) | eq[w];
-        u32 const hp = vn[w] | ~(d0 | vp[w]);
-        u32 const hn = vp[w] & d0 & ~boundary.top(w);
-        // Shift the horizontal deltas up by one row; bit 0 of word 0 takes the constant `+1` of DP row zero.
+        if constexpr (paired) hn_shifted = bitop3<0x94>(sum, kept, eq[w]);      // (sum ^ K* ^ Eq) & ~(Eq & ~K*)
+        else if constexpr (spelled_carries_) hn_shifted = bitop3<0x96>(sum, kept, eq[w]); // sum ^ K ^ Eq: the carries into every bit
+        else hn_shifted = sum ^ kept ^ eq[w]; // (left to the compiler, which spends a v_xor more per word-step on it: hip/myers_rerank.hip
+                                              // pays that full-rate op to keep its registers)
+        u32 const hp = bitop3<0xf1>(vn[w], sum, kept);                          // VN | ~(sum | K)
+        // Shift HP up by one row; bit 0 of word 0 takes the constant `+1` of DP row zero.
         u32 const hp_shifted = w == 0 ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
-        u32 const hn_shifted = w == 0 ? (hn << 1) : __builtin_amdgcn_alignbit(hn, hn_below, 31);
-        hp_below = hp, hn_below = hn;
-        vp[w] = hn_shifted | ~(xv | hp_shifted);
-        vn[w] = hp_shifted & xv & ~boundary.separator(w);
+        hp_below = hp;
+        vp[w] = bitop3<0xf1>(hn_shifted, xv, hp_shifted);                       // HNs | ~(X | HPs)
+        if constexpr (paired) vn[w] = bitop3<0x40>(hp_shifted, xv, boundary.separators[w]); // HPs & X~ & ~Msep
+        else vn[w] = hp_shifted & xv;
         // Both new vectors materialised here: without this LLVM folds VP' into the next column's `Eq & VP` and then keeps
         // `xv | hp_shifted` AND VP' alive - one v_or more per word-step (and scratch in the fused kernel).  Not for one word,
         // nor where `materialise_` is false (the tiny-token kernel): there the barrier only splits the v_lshl_or_b32 of

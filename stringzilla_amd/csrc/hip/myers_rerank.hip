@@ -45,7 +45,10 @@ __device__ __forceinline__ void rerank_rows(u32 *table, listed_row_t const &row,
             [&](u32 symbol, u32) {
                 u32 eq[words_];
                 load_match_masks<words_, byte_rows_k>(table, symbol, eq);
-                myers_column<words_>(vp, vn, eq);
+                // (the carries' xor left to the compiler: spelled as inline assembly it costs this kernel two VGPRs, and the
+                // 32-lane shape its sixth wavefront per SIMD.  The compiler's form is one full-rate v_xor more per word-step -
+                // 8 logic ops where the other bodies run 7 - in place of the half-rate v_alignbit that went.)
+                myers_column<words_, single_pattern_t, true, false>(vp, vn, eq);
             },
             []() { return true; });
 
