@@ -7,6 +7,8 @@
  *    (/root/reference/include/stringzillas/types.cuh:280-298,482-534; bench/similarities.cuh:303-308).
  *  - szs_rocm_last_pairing, szs_rocm_pair_rule_probe : which two queries shared a workgroup of the short launch that plans itself
  *    (csrc/hip/pair_rule.h) - what the last call's sorter chose, and the same choice on bare lengths without a GPU.
+ *  - szs_rocm_corner_cut_probe  : the text columns in which the short Myers bodies skip an end word of the bit-vector
+ *    (csrc/hip/corner_cut.h), on bare lengths without a GPU.
  *  - szs_rocm_shard_rows        : longest-processing-time assignment of query rows to N GPUs;
  *    the reference has no multi-GPU path at all (one engine call = one device, stringzillas.h:137).
  *  - szs_rocm_rerank_probe, szs_rocm_plan_probe, szs_rocm_orientation_probe, szs_rocm_team_orientation_probe, szs_rocm_launch_order_probe,
@@ -86,6 +88,18 @@ SZ_API_RUNTIME sz_u32_t szs_rocm_last_pairing(void *engine);
 #define SZS_ROCM_PAIR_RULE_CHOOSE 0xFFFFFFFFu
 SZ_API_RUNTIME sz_status_t szs_rocm_pair_rule_probe(sz_u32_t const *lengths, sz_size_t count, sz_u32_t *rule, sz_u64_t *total_words,
                                                     sz_u32_t *slot_pairs_out);
+
+/**
+ *  Which text columns of the short Myers bodies may leave an end word of the bit-vector untouched (csrc/hip/corner_cut.h), on bare
+ *  lengths, without a GPU: a vector of `words` words holding a query of `first_length` bytes and - unless `second_length` is
+ *  SZS_ROCM_NO_SECOND_QUERY - two separator rows and a second query above it, against the texts of one wavefront, the shortest of
+ *  `n_short` and the longest of `n_long` bytes.  Columns counted from 0: those below `*head_until` may skip the top word, those from
+ *  `*late_from` on the bottom word (SZS_ROCM_CORNER_CUT_NEVER: none does).  Fewer than three words: 0 and never.
+ */
+#define SZS_ROCM_NO_SECOND_QUERY 0xFFFFFFFFu
+#define SZS_ROCM_CORNER_CUT_NEVER 0xFFFFFFFFu
+SZ_API_RUNTIME sz_status_t szs_rocm_corner_cut_probe(sz_u32_t first_length, sz_u32_t second_length, sz_u32_t words, sz_u32_t n_short,
+                                                     sz_u32_t n_long, sz_u32_t *head_until, sz_u32_t *late_from);
 
 /**
  *  Deals `rows` query rows to `shards` devices so that the summed `row_weights` per shard are as equal as the

@@ -123,6 +123,7 @@ SIGNATURES = {
     "szs_rocm_last_call_profile": (c_int, [c_void_p, ctypes.POINTER(CallProfile)]),
     "szs_rocm_last_pairing": (ctypes.c_uint32, [c_void_p]),
     "szs_rocm_pair_rule_probe": (c_int, [c_void_p, c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), c_void_p]),
+    "szs_rocm_corner_cut_probe": (c_int, [ctypes.c_uint32] * 5 + [ctypes.POINTER(ctypes.c_uint32)] * 2),
     "szs_rocm_shard_rows": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     "szs_rocm_shard_triangle": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
     "szs_rocm_plan_probe": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -278,6 +279,21 @@ def pair_rule_probe(lengths, rule=PAIR_RULE_CHOOSE):
     if status != 0:
         raise StringZillasError(status, None)
     return int(chosen.value), int(total.value), slot_pairs.astype(np.int64) - (slot_pairs == 0xFFFFFFFF) * (1 << 32)
+
+
+CORNER_CUT_NEVER = 0xFFFFFFFF
+
+
+def corner_cut_probe(first_length, second_length, words, n_short, n_long):
+    """`szs_rocm_corner_cut_probe`: the text columns (counted from 0) in which the short Myers bodies leave an end word of a
+    `words`-word bit-vector untouched - no GPU involved.  `second_length`: None for a single query.  Returns (head_until, late_from):
+    columns below head_until skip the top word, columns from late_from on the bottom word (CORNER_CUT_NEVER: none does)."""
+    head, late = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    status = lib.szs_rocm_corner_cut_probe(first_length, 0xFFFFFFFF if second_length is None else second_length, words, n_short, n_long,
+                                           ctypes.byref(head), ctypes.byref(late))
+    if status != 0:
+        raise StringZillasError(status, None)
+    return int(head.value), int(late.value)
 
 
 def team_shapes():

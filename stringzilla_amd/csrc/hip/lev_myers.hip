@@ -40,6 +40,8 @@
 
 #define SZS_PAIR_RULE_FN __host__ __device__ static inline
 #include "pair_rule.h"
+#define SZS_CORNER_CUT_FN __host__ __device__ static inline
+#include "corner_cut.h"
 
 #include <cstdlib>
 
@@ -50,6 +52,10 @@ namespace szs_hip {
 #endif
 #ifndef SZS_MYERS_PAIR_RULES
 #define SZS_MYERS_PAIR_RULES 1 // 0: the sorter always publishes rule 0, slot s with s + ceil(Q / 2) (the A/B build of the pairing rule)
+#endif
+
+#ifndef SZS_MYERS_CUT_CORNERS
+#define SZS_MYERS_CUT_CORNERS 1 // 0: every column of the short bodies updates every word (the A/B build of the head and late loops)
 #endif
 
 #ifndef SZS_MYERS_SHORT_TEXT_DWORDS
@@ -69,6 +75,12 @@ namespace szs_hip {
  *    - ragged tail (from the wavefront's shortest text to its longest): every column is predicated on
  *      `column < text length`, finished lanes are simply masked off.
  *  Candidates arrive length-sorted, so the ragged tail is a handful of columns unless the batch itself is ragged.
+ *
+ *  The byte bodies of three words and more that take several text dwords an iteration (the short kernels) run the main loop in
+ *  three PHASES (corner_cut.h): a head loop that leaves the top word alone while its rows lie below every path the distance can
+ *  take, the full-width loop, and a late loop that leaves the bottom word alone once its rows lie above every such path.  Both
+ *  bounds are scalars of the wavefront, from its shortest and its longest text; a wider band is always safe, so each loop
+ *  hands over at an iteration boundary.
  *
  *  @tparam words_        32-bit words of the pattern bit-vector; the query fits in 32 * words_ symbols.
  *  @tparam text_dwords_  text dwords consumed per main-loop iteration: 4 for short patterns, 1 for long ones to keep
@@ -203,13 +215,18 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
         vn[w] = 0;
     }
 
-    // One DP column: the match masks of `symbol` (a byte, or a rune looked up through the rune table) update VP / VN.
-    auto take = [&](u32 symbol) {
+    // One DP column: the match masks of `symbol` (a byte, or a rune looked up through the rune table) update VP / VN -
+    // words [first_word, last_word) of them (two std::integral_constant; the whole vector outside the head and late loops).
+    auto take_words = [&](u32 symbol, auto first_word, auto last_word) {
+        constexpr int first = decltype(first_word)::value, last = decltype(last_word)::value;
         u32 eq[words_];
-        load_match_masks<words_, rows>(peq, !runes_ ? symbol : alphabet ? keys[symbol] : find_rune_slot(keys, symbol), eq);
-        if constexpr (paired_) myers_column<words_>(vp, vn, eq, boundary);
-        else myers_column<words_>(vp, vn, eq);
+        load_match_masks<words_, rows, first, last>(peq, !runes_ ? symbol : alphabet ? keys[symbol] : find_rune_slot(keys, symbol), eq);
+        if constexpr (paired_) myers_column<words_, pattern_pair_t<words_>, true, true, first, last>(vp, vn, eq, boundary);
+        else myers_column<words_, single_pattern_t, true, true, first, last>(vp, vn, eq);
     };
+    constexpr std::integral_constant<int, 0> word_zero{};
+    constexpr std::integral_constant<int, words_> word_end{};
+    auto take = [&](u32 symbol) { take_words(symbol, word_zero, word_end); };
 
     u32 column = 0;
     if constexpr (runes_) {
@@ -248,12 +265,20 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
         // Measured on MI355X: index-clamped (branch-free) reads help the one-dword loops of the long kernels; the
         // 16-column batches of the short kernels schedule better with the predicated reads.
         constexpr bool clamped_reads = SZS_MYERS_CLAMPED_READS(text_dwords_);
+        // (the long launches, one dword an iteration, keep their one loop)
+        constexpr bool phases = SZS_MYERS_CUT_CORNERS && !runes_ && words_ >= (int)SZS_CORNER_CUT_WORDS_LEAST && text_dwords_ > 1;
+        constexpr std::integral_constant<int, phases ? 1 : 0> word_one{};
+        constexpr std::integral_constant<int, phases ? words_ - 1 : words_> word_top{};
+        u32 head_until = 0, late_from = SZS_CORNER_CUT_NEVER;
+        if constexpr (phases)
+            szs_corner_cut(first_length, second_length, paired_, words_, (u32)__builtin_amdgcn_readfirstlane((int)shortest_in_wave),
+                           (u32)__builtin_amdgcn_readfirstlane((int)longest_in_wave), &head_until, &late_from);
         if (columns_per_iteration <= shortest_in_wave && longest_in_wave && query_length) {
             u32 ahead[text_dwords_];
 #pragma unroll
             for (int d = 0; d < text_dwords_; ++d) ahead[d] = clamped_reads ? text.raw_clamped(1 + d) : text.raw(1 + d);
-            for (; column + columns_per_iteration <= shortest_in_wave;
-                 column += columns_per_iteration, dword += text_dwords_) {
+            // One iteration over words [first_word, last_word): the look-ahead stream is carried from loop to loop.
+            auto batch = [&](auto first_word, auto last_word) {
                 u32 symbols[text_dwords_];
                 symbols[0] = text.splice(raw_low, ahead[0]);
 #pragma unroll
@@ -265,8 +290,19 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
                     ahead[d] = clamped_reads ? text.raw_clamped(dword + text_dwords_ + 1 + d)
                                              : text.raw(dword + text_dwords_ + 1 + d);
 #pragma unroll
-                for (int step = 0; step < 4 * text_dwords_; ++step) take((symbols[step / 4] >> (8 * (step % 4))) & 0xFFu);
+                for (int step = 0; step < 4 * text_dwords_; ++step)
+                    take_words((symbols[step / 4] >> (8 * (step % 4))) & 0xFFu, first_word, last_word);
+                column += columns_per_iteration, dword += text_dwords_;
+            };
+            if constexpr (phases) { // ---- the head loop: the top word waits
+                u32 const shortest = (u32)__builtin_amdgcn_readfirstlane((int)shortest_in_wave);
+                u32 const head_end = head_until < shortest ? head_until : shortest;
+                while (column + columns_per_iteration <= head_end) batch(word_zero, word_top);
             }
+            // ---- the main loop; with phases, up to the first iteration boundary at or beyond `late_from`
+            while (column + columns_per_iteration <= shortest_in_wave && (!phases || column < late_from)) batch(word_zero, word_end);
+            if constexpr (phases) // ---- the late loop: the bottom word is done
+                while (column + columns_per_iteration <= shortest_in_wave) batch(word_one, word_end);
         }
 #ifndef SZS_MYERS_MID_LOOP
 #define SZS_MYERS_MID_LOOP 0
@@ -294,6 +330,12 @@ __device__ __forceinline__ void myers_workgroup(u32 *peq, u32 *keys, szs_string_
                 u32 const after = text.raw(dword + 2);
                 u32 const symbols = text.splice(raw_low, next);
                 raw_low = next, next = after;
+                if (phases && column >= late_from) { // (uniform, outside the per-lane predicates)
+#pragma unroll
+                    for (int step = 0; step < 4; ++step)
+                        if (column + step < text_length) take_words((symbols >> (8 * step)) & 0xFFu, word_one, word_end);
+                    continue;
+                }
 #pragma unroll
                 for (int step = 0; step < 4; ++step)
                     if (column + step < text_length) take((symbols >> (8 * step)) & 0xFFu);

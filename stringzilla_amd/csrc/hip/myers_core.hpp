@@ -41,14 +41,22 @@ __device__ __forceinline__ u32 find_rune_slot(u32 const *keys, u32 rune) {
     }
 }
 
-template <int words_, int rows_>
+/** The match masks of `symbol`, words [first_word_, last_word_) of them: a 16-byte chunk of the row that holds none of those
+ *  words is not read (myers_column's word range: with 5 or 9 words the top word is alone in its chunk). */
+template <int words_, int rows_, int first_word_ = 0, int last_word_ = words_>
 __device__ __forceinline__ void load_match_masks(u32 const *peq, u32 symbol, u32 (&eq)[words_]) {
     using layout = peq_layout<words_, rows_>;
+    static_assert(0 <= first_word_ && first_word_ < last_word_ && last_word_ <= words_, "a word range inside the vector");
     if constexpr (layout::chunk_words == 4) {
         uint4 const *rows = reinterpret_cast<uint4 const *>(peq);
 #pragma unroll
         for (int chunk = 0; chunk < layout::chunks; ++chunk) {
+            if (chunk * 4 + 4 <= first_word_ || chunk * 4 >= last_word_) continue;
             uint4 const row = rows[chunk * rows_ + symbol];
+            // A range that begins inside the chunk still takes it in ONE ds_read_b128 (its first word is "used" by an empty
+            // statement): left to itself the compiler reads the words above `first_word_` with a ds_read2_b32 and a ds_read_b32,
+            // and pays a v_or for the second address.
+            if (chunk * 4 < first_word_) asm volatile("" : : "v"(row.x));
             if (chunk * 4 + 0 < words_) eq[chunk * 4 + 0] = row.x;
             if (chunk * 4 + 1 < words_) eq[chunk * 4 + 1] = row.y;
             if (chunk * 4 + 2 < words_) eq[chunk * 4 + 2] = row.z;
@@ -114,15 +122,25 @@ __device__ __forceinline__ u32 bitop3(u32 a, u32 b, u32 c) {
  *  holds the s0 bit, which K* = (Eq | VP) & ~Ms0 drops again: `Eq = 1, K* = 0` then happens at s0 and nowhere else (Eq is part
  *  of K on every other row), and HNs = (sum ^ K* ^ Eq) & ~(Eq & ~K*) is 0 there - q1's top row hands its carry to nobody.
  *  The sum never sees the bit (Eq & VP, VP = 0 at s0): s0 swallows the carry, s1 sees none and - sum = K* = 0 - gives q2's
- *  first row HPs = 1, HNs = 0: exactly DP row zero, as bit 0 of the vector gets it. */
-template <int words_, typename boundary_t = single_pattern_t, bool materialise_ = true, bool spelled_carries_ = true>
+ *  first row HPs = 1, HNs = 0: exactly DP row zero, as bit 0 of the vector gets it.
+ *
+ *  A word range [first_word_, last_word_) updates those words alone; the others are neither read nor written (hip/corner_cut.h
+ *  says in which columns no path of the distance needs them).  A top word left out keeps its state - before its first update
+ *  VP all ones, VN zero: "from the row below, straight down", a real path - and later joins the chain with the addc's carry and the
+ *  HP bit of the word below, as ever.  With a bottom word left out the chain starts at `first_word_` with no carry and a 1 entering
+ *  bit 0 of HPs: a horizontal delta of +1 on the frozen word's top row, "one more insertion", a real path too - what bit 0 of word
+ *  0 gets, and Hyyro's block boundary (myers_strip_column with hp_in = 1, hn_in = 0).  len(text) + popcount(VP) - popcount(VN) over
+ *  ALL words still is the distance: the frozen word's deltas and the +1 per column since then telescope to the same sum. */
+template <int words_, typename boundary_t = single_pattern_t, bool materialise_ = true, bool spelled_carries_ = true, int first_word_ = 0,
+          int last_word_ = words_>
 __device__ __forceinline__ void myers_column(u32 (&vp)[words_], u32 (&vn)[words_], u32 const (&eq)[words_],
                                              boundary_t const &boundary = {}) {
     constexpr bool paired = !std::is_same<boundary_t, single_pattern_t>::value;
     static_assert(spelled_carries_ || !paired, "a pair's HNs is not a function the compiler finds by itself");
+    static_assert(0 <= first_word_ && first_word_ < last_word_ && last_word_ <= words_, "a word range inside the vector");
     u32 carry = 0, hp_below = 0;
 #pragma unroll
-    for (int w = 0; w < words_; ++w) {
+    for (int w = first_word_; w < last_word_; ++w) {
         u32 xv, kept, hn_shifted;
         if constexpr (paired) {
             xv = bitop3<0xfe>(eq[w], vn[w], boundary.separators[w]);   // Eq | VN | Msep
@@ -138,8 +156,8 @@ __device__ __forceinline__ void myers_column(u32 (&vp)[words_], u32 (&vn)[words_
         else hn_shifted = sum ^ kept ^ eq[w]; // (left to the compiler, which spends a v_xor more per word-step on it: hip/myers_rerank.hip
                                               // pays that full-rate op to keep its registers)
         u32 const hp = bitop3<0xf1>(vn[w], sum, kept);                          // VN | ~(sum | K)
-        // Shift HP up by one row; bit 0 of word 0 takes the constant `+1` of DP row zero.
-        u32 const hp_shifted = w == 0 ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
+        // Shift HP up by one row; bit 0 of word 0 takes the constant `+1` of DP row zero (and so does the first word of a range).
+        u32 const hp_shifted = w == first_word_ ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
         hp_below = hp;
         vp[w] = bitop3<0xf1>(hn_shifted, xv, hp_shifted);                       // HNs | ~(X | HPs)
         if constexpr (paired) vn[w] = bitop3<0x40>(hp_shifted, xv, boundary.separators[w]); // HPs & X~ & ~Msep

@@ -8,6 +8,7 @@
  */
 #include "szs_internal.h"
 #include "../hip/pair_rule.h"
+#include "../hip/corner_cut.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -304,6 +305,18 @@ sz_status_t szs_rocm_pair_rule_probe(sz_u32_t const *lengths, sz_size_t count, s
             slot_pairs_out[2 * slot] = slot,
                                slot_pairs_out[2 * slot + 1] = slot < seconds ? szs_pair_second_rank(chosen, slot, slots, seconds) : 0xFFFFFFFFu;
     free(ranked);
+    return sz_success_k;
+}
+
+/* The phase bounds of myers_workgroup (hip/lev_myers.hip) on bare lengths, through the same header. */
+sz_status_t szs_rocm_corner_cut_probe(sz_u32_t first_length, sz_u32_t second_length, sz_u32_t words, sz_u32_t n_short, sz_u32_t n_long,
+                                      sz_u32_t *head_until, sz_u32_t *late_from) {
+    int const paired = second_length != SZS_ROCM_NO_SECOND_QUERY;
+    if (!head_until || !late_from || n_short > n_long) return sz_status_unknown_k;
+    if ((sz_u64_t)first_length + (paired ? (sz_u64_t)second_length + 2u : 0u) > 32ull * words) return sz_unexpected_dimensions_k;
+    unsigned head = 0, late = 0;
+    szs_corner_cut(first_length, paired ? second_length : 0u, paired, words, n_short, n_long, &head, &late);
+    *head_until = head, *late_from = late;
     return sz_success_k;
 }
 
