@@ -23,6 +23,9 @@
  *  - szs_rocm_fuzzy_find*       : the best match of a query INSIDE each listed candidate - fewest edits to some substring, and where it
  *    ends - for a snippet in a document, a primer in a read, a misspelled name in a record (csrc/host/fuzzy_find.c).
  *  - szs_rocm_fuzzy_find_spans* : the same call with the whole span: where that best match starts as well.
+ *  - szs_rocm_alignments*       : WHICH edits - per listed pair the edit script `= X I D` of the query against the candidate, or
+ *    against the span of it that szs_rocm_fuzzy_find_spans* or szs_rocm_fuzzy_scan_occurrences* found: what differs between a snippet
+ *    and the place it was found, the mismatches of a primer, the correction of a name (csrc/host/alignments.c).
  *  - szs_rocm_fuzzy_search*     : the k candidates of a corpus that contain the best such match per query, without the matrix
  *    (csrc/host/fuzzy_search.c); szs_rocm_fuzzy_search_probe reports how a call would be cut.
  *  - szs_rocm_fuzzy_scan*       : the best match of every query inside ONE long text, the text cut over the device's lanes
@@ -260,6 +263,60 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_find_spans_u64tape(void *engine, szs_d
                                                              sz_sequence_u64tape_t const *candidates, sz_size_t const *indices,
                                                              sz_size_t k, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
                                                              sz_size_t row_stride, char const **error_message);
+
+/**
+ *  ALIGNMENTS: which edits.  For slot (q, r) let c = candidates[indices[q * row_stride + r]] of n bytes, s = c[start : end] of t bytes
+ *  where `starts` and `ends` are given (start = starts[q * row_stride + r], end likewise), else s = c, and m = len(queries[q]).  S is
+ *  the unit-cost SUFFIX DP of q and s:
+ *      S[m][j] = t - j,  S[i][t] = m - i,  S[i][j] = min(S[i+1][j+1] + (q[i] != s[j]), S[i+1][j] + 1, S[i][j+1] + 1).
+ *  The CANONICAL script is the walk from (0, 0) to (m, t) that takes, at (i, j), the first of these that holds:
+ *      1. i < m, j < t and S[i+1][j+1] + (q[i] != s[j]) == S[i][j]:  '=' if the bytes are equal, else 'X' - one byte of each string;
+ *      2. i < m and S[i+1][j] + 1 == S[i][j]:                        'I' - a byte of the query alone;
+ *      3. otherwise:                                                 'D' - a byte of the candidate alone.
+ *  The letters are those of extended CIGAR with the query as the read.  Per slot the call writes
+ *      distances[q * row_stride + r] = S[0][0] = lev(q, s);
+ *      lengths[q * row_stride + r]   = L, the number of ops: max(m, t) <= L <= m + t;
+ *      ops[(q * row_stride + r) * capacity + 0 .. L)       = the script in forward order, the ASCII bytes `= X I D`;
+ *      ops[(q * row_stride + r) * capacity + L .. capacity) = 0.
+ *  L > capacity: `lengths` still holds L, all `capacity` bytes of the slot are zero and the call succeeds - the rule `counts` and
+ *  `limit` follow in the scans.  `capacity` 0 with `ops` NULL returns distances and lengths only; `ops` NULL with a capacity above 0
+ *  is refused (sz_status_unknown_k).  `distances` and `lengths` are required.  `starts` and `ends` are both NULL or both given: exactly
+ *  one is refused with sz_status_unknown_k.
+ *
+ *  Everything else is szs_rocm_fuzzy_find_spans': rows and slots (`indices`, `starts`, `ends`, `distances` and `lengths` share
+ *  `row_stride`, in cells; `ops` has `capacity` bytes per cell of that layout), k >= 1 and row_stride >= k, cells and `ops` slots at
+ *  [k, row_stride) left untouched, the dense form (`indices` NULL, k = the candidates' count), the self form (`candidates` NULL), index
+ *  validation on the host where it can read the indices and in the kernel before every use otherwise, the memory kinds of every
+ *  array, a synchronous call on the scope's stream.  An EMPTY slot is an index of SZ_SIZE_MAX or - with spans - start = end =
+ *  SZ_SIZE_MAX: distance 0, length 0, zero ops, no string touched; so the (rows, limit) matrices of
+ *  szs_rocm_fuzzy_scan_occurrences go straight in over [text] with an all-zero index matrix.
+ *
+ *  LIMITS, each refused as szs_rocm_fuzzy_find refuses its own.  The engine is not a unit-cost byte Levenshtein engine:
+ *  sz_status_unknown_k, nothing written.  A query above 256 bytes: sz_unexpected_dimensions_k, before anything is launched.  A span -
+ *  or, without spans, a whole candidate - above 512 bytes: sz_unexpected_dimensions_k; 512 is a design bound, m + distance <= 512 is
+ *  all a span from this library can be.  `starts` and `ends` are values the kernel reads from memory the caller owns:
+ *  start <= end <= n is checked before they address anything, else the call fails with sz_unexpected_dimensions_k.
+ *
+ *  All rows of up to 2^20 queries are ONE launch (csrc/hip/myers_alignments.hip): the pass of the spans over the reversed strings
+ *  with every column's trace kept, then one walk per pair.  The trace lives in an engine buffer that does not grow with the call - at
+ *  most 256 MiB of workgroup regions, each reused for every row its workgroup serves (the `align_trace_kib` knob: another budget).
+ *  szs_rocm_last_call_profile reports pairs (non-empty slots), cells (m x t over them), launches = 1 per block, and bytes that
+ *  include the L ops of every pair.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_alignments(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                               sz_sequence_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                               sz_size_t const *starts, sz_size_t const *ends, sz_size_t *distances, sz_size_t *lengths,
+                                               sz_u8_t *ops, sz_size_t capacity, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_alignments_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                       sz_sequence_u32tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                       sz_size_t const *starts, sz_size_t const *ends, sz_size_t *distances,
+                                                       sz_size_t *lengths, sz_u8_t *ops, sz_size_t capacity, sz_size_t row_stride,
+                                                       char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_alignments_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                       sz_sequence_u64tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                                       sz_size_t const *starts, sz_size_t const *ends, sz_size_t *distances,
+                                                       sz_size_t *lengths, sz_u8_t *ops, sz_size_t capacity, sz_size_t row_stride,
+                                                       char const **error_message);
 
 /**
  *  Fuzzy SEARCH: which candidates of a corpus contain something close to the query?  Row q receives the k candidates with the
@@ -696,6 +753,8 @@ SZ_API_RUNTIME sz_status_t szs_rocm_node_scores_u64tape(szs_rocm_node_engine_t e
  *  up to a multiple of 64; automatic: enough workgroups to fill the device four times over),
  *  "fuzzy_scan_piece" (n: the bytes of the text one lane of hip/myers_fuzzy_scan.hip owns in a fuzzy scan, rounded up to a multiple
  *  of 64; automatic: enough wavefronts to fill the device four times over, at least 4096 bytes),
+ *  "align_trace_kib" (n: the KiB of trace memory an alignments call may hold, at least one workgroup's region; 0 or automatic:
+ *  256 MiB),
  *  "queues" (see below), "roctx" (1: the host phases of every call - plan, decide, enqueue, wait - as roctx ranges for a
  *  `rocprofv3 --marker-trace` timeline; the marker library is looked up at run time, never linked),
  *  "cpu_requests" (strict | gpu: serve capability

@@ -486,6 +486,118 @@ class _Engine:
         host = results[:, :rows].cpu().numpy() if isinstance(results, torch.Tensor) else results[:, :rows, :k]
         return tuple(matrix.view(np.uint64) for matrix in host)
 
+    def align(self, queries, candidates, indices=None, starts=None, ends=None, capacity=None, device: Optional[DeviceScope] = None,
+              out=None):
+        """WHICH edits (`szs_rocm_alignments_*`): returns `(distances, lengths, ops)` - two `uint64` `(rows, k)` NumPy matrices and a
+        `uint8` `(rows, k, capacity)` array.  Slot `(q, r)` pairs `queries[q]` with `c = candidates[indices[q, r]]`, or with
+        `c[starts[q, r]:ends[q, r]]` where `starts` and `ends` are given (both or neither: what `fuzzy_find(..., starts=True)` and
+        `fuzzy_scan_occurrences` return): `distances` is their Levenshtein distance, `lengths` the number `L` of ops of the canonical
+        edit script, `ops[q, r, :L]` that script in forward order as the bytes `= X I D` (extended CIGAR, the query as the read; 'I'
+        is a byte of the query alone, 'D' one of the candidate alone) and zeros behind it.  A script of more than `capacity` ops keeps
+        its `L` and leaves its slot all zero.  `capacity` None: the longest query plus min(512, the longest candidate), which every
+        script fits - or, with `out`, what its `ops` holds; 0: distances and lengths only, `ops` comes back None.
+        `indices` and `candidates` None are `fuzzy_find`'s; an index of 2**64 - 1 or a span of (2**64 - 1, 2**64 - 1) is an empty slot
+        (0, 0, zeros).  `out`: a triple of NumPy arrays or torch tensors - the two matrices of 8-byte cells share the row stride of
+        `indices`, `ops` is contiguous in its last two dimensions with the same row stride in slots - filled and returned.
+        Unit-cost byte Levenshtein engines only, queries of at most 256 bytes, spans (or whole candidates) of at most 512."""
+        import torch
+
+        queries = _as_strs(queries)
+        candidates = None if candidates is None else _as_strs(candidates)
+        rows = len(queries)
+        if (starts is None) != (ends is None):
+            raise ValueError("`starts` and `ends` must both be given, or neither")
+        stride, k = None, None
+        if indices is None and (candidates is None or len(candidates) < 1):
+            raise ValueError("`indices` None needs at least one candidate; `candidates` None needs `indices`")
+        if indices is None:
+            k = len(candidates)
+        input_pointers = []
+        for matrix, name in ((indices, "indices"), (starts, "starts"), (ends, "ends")):
+            if matrix is None:
+                input_pointers.append(None)
+                continue
+            pointer, own_stride, shape = _listed_cells(matrix, name, None if k is None else (rows, k))
+            if shape[0] != rows:
+                raise ValueError(f"`{name}` must have one row per query: {shape[0]} rows, {rows} queries")
+            if stride is not None and own_stride != stride:
+                raise ValueError("`indices`, `starts` and `ends` must share one row stride")
+            stride, k = own_stride, shape[1]
+            input_pointers.append(pointer)
+        if capacity is not None and (isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or capacity < 0):
+            raise ValueError(f"capacity must be a non-negative integer, got {capacity!r}")
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("`out` must be a triple (distances, lengths, ops)")
+            output_pointers = []
+            for matrix, name in zip(out[:2], ("out distances", "out lengths")):
+                pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
+                if stride is not None and own_stride != stride:
+                    raise ValueError("`out` and `indices` must share one row stride")
+                stride = own_stride
+                output_pointers.append(pointer)
+            ops = out[2]
+            if ops is None:
+                if capacity:
+                    raise ValueError("`out` ops must not be None when the capacity is not zero")
+                capacity, ops_pointer = 0, None
+            else:
+                if isinstance(ops, np.ndarray):
+                    shape, itemsize, strides, ops_pointer = ops.shape, ops.dtype.itemsize, ops.strides, ops.ctypes.data
+                elif type(ops).__module__.partition(".")[0] == "torch" and hasattr(ops, "data_ptr"):
+                    shape, itemsize, strides, ops_pointer = tuple(ops.shape), ops.element_size(), tuple(ops.stride()), ops.data_ptr()
+                    if ops.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
+                        torch.cuda.current_stream(ops.device).synchronize()
+                else:
+                    raise ValueError(f"`out` ops must be a NumPy array or a torch tensor, got {type(ops).__name__}")
+                if capacity is None and len(shape) == 3:
+                    capacity = shape[2]
+                if len(shape) != 3 or shape != (rows, k, capacity) or itemsize != 1 or capacity < 1 or (
+                        capacity > 1 and strides[2] != 1) or (k > 1 and strides[1] != capacity) or (rows > 1 and strides[0] != stride * capacity):
+                    raise ValueError("`out` ops must be a (rows, k, capacity) array of bytes, contiguous in its last two dimensions, "
+                                     "that shares the row stride of the matrices")
+        if capacity is None:
+            pool = queries if candidates is None else candidates
+            longest = lambda strs: int(np.diff(strs.offsets.astype(np.int64)).max()) if len(strs) else 0  # noqa: E731
+            capacity = longest(queries) + min(512, longest(pool))
+        capacity = int(capacity)
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        named = (("indices", indices), ("starts", starts), ("ends", ends)) + (tuple(zip(("out distances", "out lengths", "out ops"), out))
+                                                                               if out is not None else ())
+        for name, matrix in named:
+            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
+                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
+        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
+            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        if out is None:
+            if stride is None or stride == k:
+                stride = k
+                cells = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+                scripts = torch.empty((max(rows, 1), k, capacity), dtype=torch.uint8, device=torch.device("cuda", gpu_device))
+                output_pointers, ops_pointer = [matrix.data_ptr() for matrix in cells], scripts.data_ptr() if capacity else None
+            else:  # the outputs share the stride of the inputs: host arrays as wide as theirs
+                cells = np.zeros((2, max(rows, 1), stride), dtype=np.int64)
+                scripts = np.zeros((max(rows, 1), stride, capacity), dtype=np.uint8)
+                output_pointers, ops_pointer = [matrix.ctypes.data for matrix in cells], scripts.ctypes.data if capacity else None
+
+        error = ctypes.c_char_p()
+        call = lib.szs_rocm_alignments_u64tape if queries.wide_offsets else lib.szs_rocm_alignments_u32tape
+        q_tape = queries._tape(gpu_device)
+        c_tape = None if candidates is None else candidates._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
+                      input_pointers[0], k, input_pointers[1], input_pointers[2], *output_pointers, ops_pointer, capacity, stride,
+                      ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        if isinstance(cells, torch.Tensor):
+            cells, scripts = cells[:, :rows].cpu().numpy(), scripts[:rows].cpu().numpy()
+        else:
+            cells, scripts = cells[:, :rows, :k], scripts[:rows, :k]
+        return cells[0].view(np.uint64), cells[1].view(np.uint64), scripts if capacity else None
+
     def fuzzy_search(self, queries, candidates=None, k=16, device: Optional[DeviceScope] = None, out=None, starts=False):
         """The `k` candidates that contain the best approximate match of every query (`szs_rocm_fuzzy_search_*`): returns
         `(indices, distances, ends)`, three `uint64` `(rows, k)` NumPy matrices - row `q` lists the candidates with the smallest

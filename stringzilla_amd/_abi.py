@@ -89,6 +89,8 @@ _FUZZY_SEARCH = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_voi
 _FUZZY_SCAN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ERR])
 _FUZZY_SCAN_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
 _FUZZY_SCAN_MATCHES = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
+_ALIGNMENTS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                        c_size_t, c_size_t, ERR])
 _FUZZY_SCAN_OCCURRENCES = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                    ERR])
 
@@ -147,6 +149,7 @@ SIGNATURES = {
     "szs_rocm_fuzzy_find": _FUZZY_FIND, "szs_rocm_fuzzy_find_u32tape": _FUZZY_FIND, "szs_rocm_fuzzy_find_u64tape": _FUZZY_FIND,
     "szs_rocm_fuzzy_find_spans": _FUZZY_FIND_SPANS, "szs_rocm_fuzzy_find_spans_u32tape": _FUZZY_FIND_SPANS,
     "szs_rocm_fuzzy_find_spans_u64tape": _FUZZY_FIND_SPANS,
+    "szs_rocm_alignments": _ALIGNMENTS, "szs_rocm_alignments_u32tape": _ALIGNMENTS, "szs_rocm_alignments_u64tape": _ALIGNMENTS,
     "szs_rocm_fuzzy_search": _FUZZY_SEARCH, "szs_rocm_fuzzy_search_u32tape": _FUZZY_SEARCH, "szs_rocm_fuzzy_search_u64tape": _FUZZY_SEARCH,
     "szs_rocm_fuzzy_search_probe": (c_int, [c_size_t, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
                                             ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
@@ -206,7 +209,8 @@ _KNOBS = {"tier": "SZS_ROCM_TIER", "swap": "SZS_ROCM_SWAP", "packed": "SZS_ROCM_
           "queue": "SZS_ROCM_QUEUE", "queue_words": "SZS_ROCM_QUEUE_WORDS", "queue_rounds": "SZS_ROCM_QUEUE_ROUNDS",
           "queue_priority": "SZS_ROCM_QUEUE_PRIORITY", "fused": "SZS_ROCM_FUSED", "tiny": "SZS_ROCM_TINY",
           "top_k_tile": "SZS_ROCM_TOP_K_TILE", "rerank": "SZS_ROCM_RERANK",
-          "fuzzy_search_segment": "SZS_ROCM_FUZZY_SEARCH_SEGMENT", "fuzzy_scan_piece": "SZS_ROCM_FUZZY_SCAN_PIECE"}
+          "fuzzy_search_segment": "SZS_ROCM_FUZZY_SEARCH_SEGMENT", "fuzzy_scan_piece": "SZS_ROCM_FUZZY_SCAN_PIECE",
+          "align_trace_kib": "SZS_ROCM_ALIGN_TRACE_KIB"}
 _knob_values = {name: os.environ.get(variable) for name, variable in _KNOBS.items()}  # what the library read when it was loaded
 
 

@@ -348,6 +348,27 @@ int szs_hip_levenshtein_fuzzy_starts(szs_rerank_side_t const *queries, szs_reran
                                      void *stream);
 
 /**
+ *  Alignments (hip/myers_alignments.hip; host/alignments.c): the edit script of every listed pair.  Slot r of
+ *  `row` pairs the query with s = candidate[start : end] (`starts` and `ends` both NULL: the whole candidate), read at
+ *  row * inputs_stride + r like the index; distances[row * outputs_stride + r] = lev(query, s), lengths[...] = L, the ops of the
+ *  canonical script, and the L bytes `= X I D` of that script in ops[(row * outputs_stride + r) * capacity ...], zeros behind them -
+ *  all `capacity` bytes zero when L > capacity.  `ops` NULL (then `capacity` must be 0): distances and lengths only.  Rows, groups,
+ *  sides, `widest`, flags and counters are hip/rerank_core.hpp's; an empty slot - an index of ~0, or `start` and `end` both ~0 -
+ *  receives 0, 0 and zeros.  start > end or end > the candidate's length addresses nothing and sets `flags[SZS_RERANK_FLAG_TAPE]`; a
+ *  span of more than SZS_ALIGN_LONGEST_SPAN bytes sets `flags[SZS_RERANK_FLAG_UNFIT]`.  `trace`: `workgroups` x
+ *  SZS_ALIGN_REGION_BYTES(widest) bytes of device memory (no need to clear it), one region per workgroup; the grid is
+ *  min(runs of 64 / lanes rows, workgroups) and a workgroup strides over the runs.  `counters`: [0] += pairs, [1] += m x t,
+ *  [2] += m + t + L.
+ */
+#define SZS_ALIGN_LONGEST_SPAN 512u
+#define SZS_ALIGN_REGION_BYTES(widest) ((size_t)64 * SZS_ALIGN_LONGEST_SPAN * (widest) * 8) /* lanes x columns x words x (VP', D0 | VN) */
+int szs_hip_levenshtein_alignments(szs_rerank_side_t const *queries, szs_rerank_side_t const *candidates, uint64_t first_query,
+                                   uint32_t const *rows, uint32_t rows_count, uint64_t const *indices, uint64_t const *starts,
+                                   uint64_t const *ends, uint64_t inputs_stride, uint64_t k, uint64_t *distances, uint64_t *lengths,
+                                   uint64_t outputs_stride, uint8_t *ops, uint64_t capacity, unsigned widest, void *trace,
+                                   uint32_t workgroups, uint32_t *flags, unsigned long long *counters, void *stream);
+
+/**
  *  A tile of the same distance for the search (hip/myers_fuzzy_tile.hip; host/fuzzy_search.c):
  *  cells[r * cells_stride + c] = the distance of query first_query + r inside candidate first_column + c, for r < rows and c < columns,
  *  8-byte cells that szs_hip_top_k_scan folds unchanged with `descending` = 0.  One one-wavefront workgroup per (row, `segment`
@@ -466,6 +487,8 @@ enum {
                                         rounded up to a multiple of 64 (host/fuzzy_search.c) */
     szs_knob_fuzzy_scan_piece_k,     /* -1 automatic | n: the bytes of the text one lane of hip/myers_fuzzy_scan.hip owns, rounded up to a
                                         multiple of 64, at least 64 (host/fuzzy_scan.c) */
+    szs_knob_align_trace_kib_k,      /* -1 or 0 automatic (SZS_ALIGN_TRACE_BYTES) | n: the KiB of trace memory an alignments call may hold -
+                                        at least one workgroup's region (host/alignments.c) */
     szs_knob_count_k
 };
 int szs_tuning_get(int knob);

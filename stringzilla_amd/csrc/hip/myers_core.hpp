@@ -220,6 +220,35 @@ __device__ __forceinline__ u32 myers_prefix_column(u32 (&vp)[words_], u32 (&vn)[
     return (hp_below >> 31) | ((hn_below >> 31) << 1);
 }
 
+/** myers_prefix_column that also hands out the column's TRACE (hip/myers_alignments.hip): `vp` leaves as VP',
+ *  bit i set iff D[i][j] = D[i-1][j] + 1, and `diagonal_zero` is the TRUE diagonal-zero vector D0 | VN with VN taken before the
+ *  update, bit i set iff D[i][j] = D[i-1][j-1].  The local `d0` below lacks the VN term: HP and HN do not need it (VN is or-ed into
+ *  HP, and VP & VN = 0 keeps it out of HN), a traceback does - where VN is set the cell equals its diagonal neighbour whatever Eq
+ *  says. */
+template <int words_>
+__device__ __forceinline__ u32 myers_prefix_column_traced(u32 (&vp)[words_], u32 (&vn)[words_], u32 const (&eq)[words_],
+                                                          u32 (&diagonal_zero)[words_]) {
+    u32 carry = 0, hp_below = 0, hn_below = 0;
+#pragma unroll
+    for (int w = 0; w < words_; ++w) {
+        u32 const xv = eq[w] | vn[w];
+        u32 carry_out;
+        u32 const sum = __builtin_addc(eq[w] & vp[w], vp[w], carry, &carry_out);
+        carry = carry_out;
+        u32 const d0 = (sum ^ vp[w]) | eq[w];
+        diagonal_zero[w] = d0 | vn[w];
+        u32 const hp = vn[w] | ~(d0 | vp[w]);
+        u32 const hn = vp[w] & d0;
+        u32 const hp_shifted = w == 0 ? ((hp << 1) | 1u) : __builtin_amdgcn_alignbit(hp, hp_below, 31);
+        u32 const hn_shifted = w == 0 ? (hn << 1) : __builtin_amdgcn_alignbit(hn, hn_below, 31);
+        hp_below = hp, hn_below = hn;
+        vp[w] = hn_shifted | ~(xv | hp_shifted);
+        vn[w] = hp_shifted & xv;
+        if constexpr (words_ > 1) asm("" : "+v"(vp[w]), "+v"(vn[w])); // as in myers_column: both new vectors materialised
+    }
+    return (hp_below >> 31) | ((hn_below >> 31) << 1);
+}
+
 /** One column of one strip; `hp_in` / `hn_in` are the deltas entering the strip's first row as 0 / 1 values; the bit pair
  *  leaving its last row comes back as hp | hn << 1. */
 template <int words_>

@@ -133,6 +133,22 @@ __device__ __forceinline__ void listed_one_strip_rows(szs_rerank_side_t const &q
 }
 
 /**
+ *  The same prologue for a workgroup that serves MORE than one run of 64 / L rows (a grid bounded by something other than the rows:
+ *  hip/myers_alignments.hip's by its trace memory): `first_slot` is the slot of the wavefront's first group, where the prologue
+ *  above takes blockIdx.x x groups.  Uniform over the wavefront.
+ */
+template <int lanes_, typename body_t>
+__device__ __forceinline__ void listed_one_strip_rows_at(szs_rerank_side_t const &queries, u64 first_query, u32 const *__restrict__ rows,
+                                                         u32 rows_count, u64 first_slot, u32 *tables, u32 table_dwords, u32 *flags,
+                                                         body_t body) {
+    u32 const group = threadIdx.x / lanes_;
+    listed_row_t const row = listed_row(queries, first_query, rows, rows_count, first_slot + group, SZS_RERANK_LONGEST_QUERY, flags);
+    u32 const longest = listed_longest_query(row);
+    u32 *const table = tables + group * table_dwords;
+    listed_at_width(longest ? (longest + 31u) / 32u : 1u, [&](auto width) { body(width, table, row); });
+}
+
+/**
  *  The Peq table of `row` at `words_` words, built by the group's `lanes_` lanes: every dword of word w starts as `fill(w)`, then
  *  byte i of the pattern sets bit `position_of(i)` of its byte's row.  One wavefront: __syncthreads() orders its LDS traffic, no
  *  s_barrier is left.

@@ -270,6 +270,7 @@ static void release_device_state(szs_engine_s *engine) {
     szs_buffer_release(&engine->device_rerank);
     szs_buffer_release(&engine->device_rerank_staged);
     szs_buffer_release(&engine->device_rerank_parked);
+    szs_buffer_release(&engine->device_align_trace);
     szs_tiny_forget(&engine->tiny[0]), szs_tiny_forget(&engine->tiny[1]), engine->narrow_zeroed = NULL;
     engine->fused_zeroed = NULL;
     if (engine->events_device >= 0) {

@@ -432,6 +432,37 @@ sz_status_t szs_rocm_fuzzy_find_spans_u64tape(void *engine, szs_device_scope_t d
     SZS_FUZZY_FIND_SPANS_BODY(input_from_u64tape)
 }
 
+/* ---- alignments (host/alignments.c) ----------------------------------------------------------------------------------- */
+
+#define SZS_ALIGNMENTS_BODY(MAKE_INPUT)                                                                                \
+    if (k < 1 || row_stride < k || !queries)                                                                           \
+        return szs_engine_alignments((szs_engine_s *)engine, (szs_scope_s *)device, NULL, NULL, indices, k, starts,    \
+                                     ends, distances, lengths, ops, capacity, row_stride, error_message);              \
+    szs_input_t const query_input = MAKE_INPUT(queries);                                                               \
+    szs_input_t candidate_input;                                                                                       \
+    if (candidates) candidate_input = MAKE_INPUT(candidates);                                                          \
+    return szs_engine_alignments((szs_engine_s *)engine, (szs_scope_s *)device, &query_input,                          \
+                                 candidates ? &candidate_input : NULL, indices, k, starts, ends, distances, lengths,   \
+                                 ops, capacity, row_stride, error_message);
+
+sz_status_t szs_rocm_alignments(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, sz_sequence_t const *candidates,
+                                sz_size_t const *indices, sz_size_t k, sz_size_t const *starts, sz_size_t const *ends, sz_size_t *distances,
+                                sz_size_t *lengths, sz_u8_t *ops, sz_size_t capacity, sz_size_t row_stride, char const **error_message) {
+    SZS_ALIGNMENTS_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_alignments_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                        sz_sequence_u32tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                        sz_size_t const *starts, sz_size_t const *ends, sz_size_t *distances, sz_size_t *lengths,
+                                        sz_u8_t *ops, sz_size_t capacity, sz_size_t row_stride, char const **error_message) {
+    SZS_ALIGNMENTS_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_alignments_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                        sz_sequence_u64tape_t const *candidates, sz_size_t const *indices, sz_size_t k,
+                                        sz_size_t const *starts, sz_size_t const *ends, sz_size_t *distances, sz_size_t *lengths,
+                                        sz_u8_t *ops, sz_size_t capacity, sz_size_t row_stride, char const **error_message) {
+    SZS_ALIGNMENTS_BODY(input_from_u64tape)
+}
+
 /* ---- fuzzy search (host/fuzzy_search.c) ------------------------------------------------------------------------------- */
 
 #define SZS_FUZZY_SEARCH_BODY(MAKE_INPUT)                                                                              \

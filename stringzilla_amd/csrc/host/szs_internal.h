@@ -173,6 +173,7 @@ typedef struct szs_engine_s {
     szs_buffer_t device_rerank;          /* device: the counters, the kernel's rows, the refs */
     szs_buffer_t device_rerank_staged;   /* device: dense indices, then scores, of a block whose arrays the device cannot reach */
     szs_buffer_t device_rerank_parked;   /* device: the parked deltas of the strips kernel, workgroups x 64 x ceil(longest candidate / 16) dwords */
+    szs_buffer_t device_align_trace;     /* device: the trace regions of an alignments call (host/alignments.c), workgroups x SZS_ALIGN_REGION_BYTES */
 
     szs_rocm_call_profile_t last_profile;
 } szs_engine_s;
@@ -410,6 +411,14 @@ sz_status_t szs_engine_fuzzy_find(szs_engine_s *engine, szs_scope_s *scope, szs_
 sz_status_t szs_engine_fuzzy_find_spans(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                                         size_t const *indices, size_t k, size_t *distances, size_t *starts, size_t *ends,
                                         size_t row_stride, char const **error_message);
+
+/* ---- alignments (alignments.c) ------------------------------------------------------------------------------------------- */
+
+/** The edit script of every listed pair (szs_rocm_alignments*): `starts` and `ends` both NULL or both given; `distances` and `lengths`
+ *  required; `ops` NULL needs `capacity` 0.  Unit-cost byte Levenshtein engines only.  Uses the engine's rerank buffers and its trace. */
+sz_status_t szs_engine_alignments(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                  size_t const *indices, size_t k, size_t const *starts, size_t const *ends, size_t *distances,
+                                  size_t *lengths, unsigned char *ops, size_t capacity, size_t row_stride, char const **error_message);
 
 /* ---- fuzzy search (fuzzy_search.c) -------------------------------------------------------------------------------------- */
 

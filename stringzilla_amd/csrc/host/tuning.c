@@ -48,6 +48,7 @@ static struct {
     [szs_knob_rerank_k] = {"rerank", "SZS_ROCM_RERANK"},
     [szs_knob_fuzzy_search_segment_k] = {"fuzzy_search_segment", "SZS_ROCM_FUZZY_SEARCH_SEGMENT"},
     [szs_knob_fuzzy_scan_piece_k] = {"fuzzy_scan_piece", "SZS_ROCM_FUZZY_SCAN_PIECE"},
+    [szs_knob_align_trace_kib_k] = {"align_trace_kib", "SZS_ROCM_ALIGN_TRACE_KIB"},
 };
 
 /** Text -> value.  -1 always means "automatic".  Tier names: lanes 0, systolic 1, chain 2; planner: host 0, device 1. */
