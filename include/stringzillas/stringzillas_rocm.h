@@ -18,6 +18,9 @@
  *  - szs_rocm_node_*            : one cross-product over the N GPUs of a host, in C (csrc/host/node.c).
  *  - szs_rocm_tuning_set        : the tuning / testing knobs.
  *  - szs_rocm_top_k*            : the k best candidates of every query, without the queries x candidates matrix (csrc/host/top_k.c).
+ *  - szs_rocm_within*           : EVERY candidate of every query inside a score bound - the full count and the leftmost `limit` hits
+ *    in fixed (queries x limit) rows (csrc/host/within.c); szs_rocm_fuzzy_search_within* answers the same for approximate substring
+ *    matches (csrc/host/fuzzy_search.c), and szs_rocm_within_probe reports how either call would be cut.
  *  - szs_rocm_rerank*           : exact scores of LISTED candidates per query - what verifies the hits of a coarse search (top-k's own
  *    `indices`, a fingerprint search, any outside candidate generator) without a queries x candidates matrix (csrc/host/rerank.c).
  *  - szs_rocm_fuzzy_find*       : the best match of a query INSIDE each listed candidate - fewest edits to some substring, and where it
@@ -147,6 +150,54 @@ SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u32tape(void *engine, szs_device_scope
 SZ_API_RUNTIME sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
                                                   sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices,
                                                   void *scores, sz_size_t row_stride, char const **error_message);
+
+/**
+ *  WITHIN: every candidate of every query inside a score bound - "everything at least this close", where szs_rocm_top_k answers
+ *  "the k best" - in one call, without materialising the queries x candidates matrix and without an output that grows with the data:
+ *      counts[q]                     = the number of hits of query q among ALL candidates (it may exceed `limit`),
+ *      indices[q * row_stride + i]   = the candidate of its i-th hit in ASCENDING candidate index, and - `scores` not NULL -
+ *      scores[q * row_stride + i]    = the score of that pair, an 8-byte cell of the engine's own type,   for i < min(counts[q], limit);
+ *  slots [min(counts[q], limit), limit) hold index SZ_SIZE_MAX and score 0 - szs_rocm_top_k's empty pair, the slot that
+ *  szs_rocm_rerank, szs_rocm_fuzzy_find and szs_rocm_alignments skip, so the rows feed them directly - and cells [limit, row_stride)
+ *  are left untouched.  `limit` 0 writes `counts` only: `indices` and `scores` may then be NULL and are not looked at.
+ *
+ *  `engine`: any engine szs_rocm_top_k takes - Levenshtein over bytes or UTF-8 at any costs, Needleman-Wunsch, Smith-Waterman.  A
+ *  DISTANCE engine hits iff bound >= 0 and score <= bound (a negative bound: no hits, and nothing is scored); NW and SW hit iff the
+ *  signed score >= bound.  `candidates` NULL: SELF-SEARCH, each query's own index excluded (duplicates at other indices count).
+ *
+ *  Refused before anything is launched, with nothing written, in this order: limit > 65,536 or row_stride < limit
+ *  (sz_unexpected_dimensions_k; the cap is a choice, not a measurement - `counts` is the full number whatever the limit); an engine that
+ *  is none of the above; NULL queries (zero queries: success, nothing is looked at); NULL `counts`; with limit > 0 a NULL `indices`
+ *  (each sz_status_unknown_k).  Zero candidates: counts of 0 and empty rows.  Candidate counts beyond 2^32 are fine.  Inputs and outputs
+ *  may live in host, pinned, unified or device memory; plain host outputs are staged densely - 2 x block x limit x 8 bytes within 128 MiB
+ *  bound the queries of a block - and copied in one 2-D copy per array.  Synchronous, also when it fails.
+ *
+ *  The call scores szs_rocm_top_k's tiles (ordinary engine calls into device scratch) and folds each with csrc/hip/within.hip: a
+ *  count pass, a store pass - not launched with limit 0 - and after the last tile one launch for the counts and the empty slots.  No
+ *  atomic decides a slot: the bytes written depend on the strings, the bound and the limit alone.  The `top_k_tile` knob caps the
+ *  candidates of a tile.  szs_rocm_last_call_profile: pairs and cells of the scoring launches; launches = scoring, count, store and
+ *  finish launches; kernel time = the scoring launches.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_within(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                           sz_sequence_t const *candidates, sz_ssize_t bound, sz_size_t limit, sz_size_t *counts,
+                                           sz_size_t *indices, void *scores, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_within_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                   sz_sequence_u32tape_t const *candidates, sz_ssize_t bound, sz_size_t limit,
+                                                   sz_size_t *counts, sz_size_t *indices, void *scores, sz_size_t row_stride,
+                                                   char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_within_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                   sz_sequence_u64tape_t const *candidates, sz_ssize_t bound, sz_size_t limit,
+                                                   sz_size_t *counts, sz_size_t *indices, void *scores, sz_size_t row_stride,
+                                                   char const **error_message);
+
+/**
+ *  How szs_rocm_within and szs_rocm_fuzzy_search_within would cut a call of these counts - host only, no GPU: the queries of a block,
+ *  the candidates of a tile, the workgroups that share a row of the fold (`segments`) and the columns of each (`segment_columns`, a
+ *  multiple of 1024; segments x segment_columns >= tile).  The `top_k_tile` knob applies as it does to the calls.  Outputs are optional.
+ *  limit > 65,536: sz_unexpected_dimensions_k.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_within_probe(sz_size_t queries_count, sz_size_t candidates_count, sz_size_t limit, sz_size_t *block,
+                                                 sz_size_t *tile, sz_size_t *segments, sz_size_t *segment_columns);
 
 /**
  *  Rerank: the exact scores of the candidates an index row LISTS per query, in one call -
@@ -369,6 +420,47 @@ SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_u64tape(void *engine, szs_devic
 SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_probe(sz_size_t queries_count, sz_size_t candidates_count, sz_size_t k,
                                                        sz_size_t longest_query, sz_size_t *block, sz_size_t *tile, sz_size_t *segment,
                                                        sz_size_t *workgroups);
+
+/**
+ *  Fuzzy search WITHIN a bound: every candidate that contains something within `max_distance` edits of the query.  A hit of query q is
+ *  a candidate whose szs_rocm_fuzzy_find distance - min over j of D[m][j] - is <= max_distance:
+ *      counts[q]                   = the number of hits among ALL candidates (it may exceed `limit`),
+ *      indices[q * row_stride + i] = the candidate of the i-th hit in ASCENDING candidate index, for i < min(counts[q], limit), and -
+ *      where the arrays are given - distances[...], ends[...], starts[...]: exactly what szs_rocm_fuzzy_find /
+ *      szs_rocm_fuzzy_find_spans return for the rows of `indices`, bit for bit;
+ *  slots [min(counts[q], limit), limit) hold (SZ_SIZE_MAX, 0, 0, 0), cells [limit, row_stride) are left untouched, and `limit` 0 writes
+ *  `counts` only - no other array is looked at.  `max_distance` is any sz_size_t: no distance exceeds the query's length, so the
+ *  kernels receive min(max_distance, 256).  A query of no bytes hits every candidate.  `candidates` NULL: SELF-SEARCH, the own index
+ *  excluded.
+ *
+ *  Engines, query lengths and statuses are szs_rocm_fuzzy_search's - a unit-cost BYTE Levenshtein engine, queries of at most 256 bytes
+ *  (a longer one fails the whole call with sz_unexpected_dimensions_k before anything is launched) - and the refusals come in its
+ *  order, with nothing written: limit > 65,536 or row_stride < limit (sz_unexpected_dimensions_k; the cap is a choice, not a
+ *  measurement); the engine; NULL queries (zero queries: success); NULL `counts`; with limit > 0 a NULL `indices`, `ends` without
+ *  `distances`, `starts` without `ends` (each sz_status_unknown_k).  Synchronous, also when it fails.
+ *
+ *  The call is szs_rocm_fuzzy_search's with the fold of csrc/hip/within.hip in place of the sorting one: the same tile kernel, the
+ *  same knobs (`top_k_tile`, `fuzzy_search_segment`), none of which changes a result; `ends` and `starts` come from the same winners
+ *  pass over the (queries x limit) index rows, and a call without `ends` or with limit 0 launches none.  szs_rocm_last_call_profile:
+ *  pairs and cells of every scored (query, candidate) plus the winners pass's (every slot of a row that holds a hit); launches =
+ *  scoring, count, store, finish and winners-pass launches; kernel time = the scoring launches.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_within(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                                        sz_sequence_t const *candidates, sz_size_t max_distance, sz_size_t limit,
+                                                        sz_size_t *counts, sz_size_t *indices, sz_size_t *distances, sz_size_t *starts,
+                                                        sz_size_t *ends, sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_within_u32tape(void *engine, szs_device_scope_t device,
+                                                                sz_sequence_u32tape_t const *queries,
+                                                                sz_sequence_u32tape_t const *candidates, sz_size_t max_distance,
+                                                                sz_size_t limit, sz_size_t *counts, sz_size_t *indices,
+                                                                sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                                sz_size_t row_stride, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_fuzzy_search_within_u64tape(void *engine, szs_device_scope_t device,
+                                                                sz_sequence_u64tape_t const *queries,
+                                                                sz_sequence_u64tape_t const *candidates, sz_size_t max_distance,
+                                                                sz_size_t limit, sz_size_t *counts, sz_size_t *indices,
+                                                                sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                                                sz_size_t row_stride, char const **error_message);
 
 /**
  *  Fuzzy SCAN: many short patterns in ONE long text - a chromosome, a book, a log file, a concatenated corpus.  For every query q

@@ -650,6 +650,106 @@ class _Engine:
             return out
         return tuple(matrix.view(np.uint64) for matrix in results[:, :rows].cpu().numpy())
 
+    def within(self, queries, candidates=None, bound=None, limit=64, device: Optional[DeviceScope] = None, out=None):
+        """EVERY candidate of every query inside a score bound (`szs_rocm_within_*`), where `top_k` answers "the k best": returns
+        `(counts, indices, scores)` - a `uint64` vector of `len(queries)`, a `uint64` and an engine-dtype `(len(queries), limit)`
+        matrix.  A distance engine hits iff `bound >= 0` and `score <= bound`, NW / SW iff the signed `score >= bound`.  `counts[q]`
+        is the number of hits among ALL candidates (it may exceed `limit`); `indices[q, i]` and `scores[q, i]` are the `i`-th hit in
+        ascending candidate index and its score, and the slots behind hold index 2**64 - 1 and score 0 - the empty slot `rerank`,
+        `fuzzy_find` and `align` skip, so the rows feed them directly.  `candidates` None: self-search, each query's own index
+        excluded.  `limit=0` counts only: the matrices have shape `(len(queries), 0)`.  `out`: a triple `(counts, indices, scores)`
+        of NumPy arrays or torch tensors of 8-byte cells - a contiguous vector and two matrices with contiguous rows of one row
+        stride - filled and returned; `scores` may be None, and with `limit=0` so may `indices`.  `limit` at most 65,536."""
+        if isinstance(bound, (bool, np.bool_)) or not isinstance(bound, (int, np.integer)) or not -2**63 <= int(bound) < 2**63:
+            raise ValueError(f"bound must be an integer of 64 signed bits, got {bound!r}")
+        return self._bounded_rows("szs_rocm_within", ("indices", "scores"), ("scores",), queries, candidates, int(bound), limit, device, out)
+
+    def fuzzy_search_within(self, queries, candidates=None, max_distance=None, limit=64, starts=False, device: Optional[DeviceScope] = None,
+                            out=None):
+        """EVERY candidate that contains something within `max_distance` edits of the query (`szs_rocm_fuzzy_search_within_*`), where
+        `fuzzy_search` answers "the k best": returns `(counts, indices, distances, ends)` - a `uint64` vector of `len(queries)` and
+        three `uint64` `(len(queries), limit)` matrices; `starts=True`: `(counts, indices, distances, starts, ends)`.  A hit is a
+        candidate whose `fuzzy_find` distance is at most `max_distance` (any non-negative integer below 2**64); `counts[q]` is their
+        number among ALL candidates, row `q` lists the leftmost `limit` of them in ascending candidate index, and `distances`, `starts`
+        and `ends` are what `fuzzy_find(queries, candidates, indices, starts=...)` returns for those rows, bit for bit.  The slots
+        behind hold `(2**64 - 1, 0, 0, 0)`.  A query of no bytes hits every candidate.  `candidates` None: self-search, the own index
+        excluded.  `limit=0` counts only.  `out`: a tuple in the order returned, as `within` takes it.  Unit-cost byte Levenshtein
+        engines only, queries of at most 256 bytes, `limit` at most 65,536."""
+        if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, np.integer)) or not 0 <= int(max_distance) < 2**64:
+            raise ValueError(f"max_distance must be a non-negative integer below 2**64, got {max_distance!r}")
+        names = ("indices", "distances", "starts", "ends") if starts else ("indices", "distances", "ends")
+        return self._bounded_rows("szs_rocm_fuzzy_search_within", names, (), queries, candidates, int(max_distance), limit, device, out)
+
+    def _bounded_rows(self, entry, names, optional, queries, candidates, bound, limit, device, out):
+        """What `within` and `fuzzy_search_within` share: the checks, a vector of counts and `len(names)` matrices of `limit` slots a
+        row behind `entry`'s tape forms (a missing `starts` goes as NULL).  `optional`: the matrices `out` may leave None."""
+        import torch
+
+        if isinstance(limit, (bool, np.bool_)) or not isinstance(limit, (int, np.integer)) or not 0 <= int(limit) <= 65536:
+            raise ValueError(f"limit must be an integer within [0, 65536], got {limit!r}")
+        limit = int(limit)
+        queries = _as_strs(queries)
+        candidates = None if candidates is None else _as_strs(candidates)
+        rows = len(queries)
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 1 + len(names):
+                raise ValueError(f"`out` must be a tuple (counts, {', '.join(names)})")
+            counts = out[0]
+            if isinstance(counts, np.ndarray):
+                shape, itemsize, unit, counts_pointer = counts.shape, counts.dtype.itemsize, counts.strides == (8,), counts.ctypes.data
+            elif type(counts).__module__.partition(".")[0] == "torch" and hasattr(counts, "data_ptr"):
+                shape, itemsize, unit, counts_pointer = tuple(counts.shape), counts.element_size(), counts.stride() == (1,), counts.data_ptr()
+            else:
+                raise ValueError(f"`out counts` must be a NumPy array or a torch tensor, got {type(counts).__name__}")
+            if shape != (rows,) or itemsize != 8 or (rows > 1 and not unit):
+                raise ValueError(f"`out counts` must be a contiguous vector of {rows} 8-byte cells")
+            pointers, stride = [], None
+            for matrix, name in zip(out[1:], names):
+                if matrix is None and (name in optional or not limit):
+                    pointers.append(None)
+                    continue
+                if not limit:  # never looked at: only the shape is checked
+                    if tuple(getattr(matrix, "shape", ())) != (rows, 0):
+                        raise ValueError(f"`out {name}` must be None or of shape ({rows}, 0) with limit 0")
+                    pointers.append(None)
+                    continue
+                pointer, own_stride, _ = _listed_cells(matrix, "out " + name, (rows, limit))
+                if stride is not None and own_stride != stride:
+                    raise ValueError("the matrices of `out` must share one row stride")
+                stride = own_stride
+                pointers.append(pointer)
+            stride = limit if stride is None else stride
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        for array, name in (tuple(zip(out, ("counts",) + names)) if out is not None else ()):
+            if getattr(array, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
+                if array.device.index != gpu_device:
+                    raise ValueError(f"`out {name}` is on {array.device}, the call runs on GPU {gpu_device}")
+                torch.cuda.current_stream(array.device).synchronize()  # torch's own stream may still be filling it
+        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
+            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        if out is None:
+            where = torch.device("cuda", gpu_device)
+            results = (torch.empty(max(rows, 1), dtype=torch.int64, device=where),
+                       torch.empty((len(names), max(rows, 1), limit), dtype=torch.int64, device=where))
+            counts_pointer, stride = results[0].data_ptr(), limit
+            pointers = [matrix.data_ptr() if limit else None for matrix in results[1]]
+        if entry == "szs_rocm_fuzzy_search_within" and "starts" not in names:
+            pointers = pointers[:2] + [None] + pointers[2:]  # (indices, distances, no starts, ends)
+
+        error = ctypes.c_char_p()
+        call = getattr(lib, entry + ("_u64tape" if queries.wide_offsets else "_u32tape"))
+        q_tape = queries._tape(gpu_device)
+        c_tape = None if candidates is None else candidates._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape), bound, limit,
+                      counts_pointer, *pointers, stride, ctypes.byref(error))
+        _abi.check(status, error)
+        if out is not None:
+            return out
+        counts, matrices = results[0][:rows].cpu().numpy().view(np.uint64), results[1][:, :rows].cpu().numpy()
+        return (counts,) + tuple(matrix.view(self._dtype if name == "scores" else np.uint64) for matrix, name in zip(matrices, names))
+
     def fuzzy_scan(self, queries, text, device: Optional[DeviceScope] = None, out=None, starts=False):
         """The best match of every query inside ONE long text (`szs_rocm_fuzzy_scan_*`): returns `(distances, ends)`, two `uint64`
         NumPy vectors of `len(queries)` - exactly column 0 of `fuzzy_find(queries, [text])`, with the text cut over the device's lanes

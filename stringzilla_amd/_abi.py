@@ -86,7 +86,10 @@ _RERANK = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c
 _FUZZY_FIND = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ERR])
 _FUZZY_FIND_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 _FUZZY_SEARCH = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
-_FUZZY_SCAN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ERR])
+_WITHIN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_ssize_t, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
+_FUZZY_SEARCH_WITHIN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_size_t, ERR])
+_FUZZY_SCAN = (c_int,[c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ERR])
 _FUZZY_SCAN_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
 _FUZZY_SCAN_MATCHES = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, ERR])
 _ALIGNMENTS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -145,6 +148,11 @@ SIGNATURES = {
     "szs_rocm_node_scores_u32tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_node_scores_u64tape": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.POINTER(NodeStats), ERR]),
     "szs_rocm_top_k": _TOP_K, "szs_rocm_top_k_u32tape": _TOP_K, "szs_rocm_top_k_u64tape": _TOP_K,
+    "szs_rocm_within": _WITHIN, "szs_rocm_within_u32tape": _WITHIN, "szs_rocm_within_u64tape": _WITHIN,
+    "szs_rocm_within_probe": (c_int, [c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                      ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "szs_rocm_fuzzy_search_within": _FUZZY_SEARCH_WITHIN, "szs_rocm_fuzzy_search_within_u32tape": _FUZZY_SEARCH_WITHIN,
+    "szs_rocm_fuzzy_search_within_u64tape": _FUZZY_SEARCH_WITHIN,
     "szs_rocm_rerank": _RERANK, "szs_rocm_rerank_u32tape": _RERANK, "szs_rocm_rerank_u64tape": _RERANK,
     "szs_rocm_fuzzy_find": _FUZZY_FIND, "szs_rocm_fuzzy_find_u32tape": _FUZZY_FIND, "szs_rocm_fuzzy_find_u64tape": _FUZZY_FIND,
     "szs_rocm_fuzzy_find_spans": _FUZZY_FIND_SPANS, "szs_rocm_fuzzy_find_spans_u32tape": _FUZZY_FIND_SPANS,
@@ -252,6 +260,18 @@ def fuzzy_search_probe(queries_count, candidates_count, k, longest_query=0):
     if status != 0:
         raise StringZillasError(status, None)
     return int(block.value), int(tile.value), int(segment.value), int(workgroups.value)
+
+
+def within_probe(queries_count, candidates_count, limit):
+    """`szs_rocm_within_probe`: how `within` and `fuzzy_search_within` would cut a call of these counts - no GPU involved.  Returns
+    (block, tile, segments, segment_columns): the queries of a block, the candidates of a tile, the workgroups that share a row of the
+    fold and the columns of each.  The `top_k_tile` knob applies as it does to the calls."""
+    block, tile, segments, segment_columns = c_size_t(0), c_size_t(0), c_size_t(0), c_size_t(0)
+    status = lib.szs_rocm_within_probe(queries_count, candidates_count, limit, ctypes.byref(block), ctypes.byref(tile),
+                                       ctypes.byref(segments), ctypes.byref(segment_columns))
+    if status != 0:
+        raise StringZillasError(status, None)
+    return int(block.value), int(tile.value), int(segments.value), int(segment_columns.value)
 
 
 def fuzzy_scan_probe(queries_count, longest_query, text_length):

@@ -251,6 +251,31 @@ int szs_hip_top_k_emit(uint64_t const *lists, uint32_t rows, uint32_t k, uint64_
                        int descending, void *stream);
 
 /**
+ *  Every candidate inside a score bound, over the same scored tiles (hip/within.hip; host/selection.c).  A
+ *  cell HITS when it is <= `bound` as an unsigned distance or - `descending` - >= `bound` as a signed score.  The tile contract is
+ *  szs_hip_top_k_scan's: `cells[r * cells_stride + c]`, column c is candidate first_column + c, `self_first_row` != ~0 skips row r's
+ *  own candidate self_first_row + r, and the tiles of a row arrive in ascending column order.
+ *
+ *  szs_hip_within_fold counts the hits of the tile - one workgroup per (row, segment of `segment_columns` columns), `segments` of them
+ *  a row with segments * segment_columns >= columns, each leaving one word of `partials` (rows * segments words) - and, with `limit`
+ *  > 0, stores hit number i of a row - counted over all tiles so far - as indices[r * stride + i] = its candidate and (`scores` not
+ *  NULL) scores[r * stride + i] = its cell, for i < limit.  `running`: the rows' hit counts before this tile; `running_next`, another
+ *  array, receives them after it - the caller swaps the two per tile and zeroes the first one when a block of rows begins.  With
+ *  `limit` 0 nothing is stored and neither array is looked at: the count pass ADDS to `partials` instead, which the caller zeroes when
+ *  a block begins, and whose geometry it keeps over the tiles.
+ *  szs_hip_within_finish writes counts[r] = running[r] + the row's `segments` partials (`segments` 0 with `limit` > 0: the running
+ *  count has them all) and fills slots [min(counts[r], limit), limit) with index ~0 and score 0: szs_hip_top_k_emit's empty pair.
+ *  limit <= SZS_WITHIN_MOST - a choice, not a measurement - and stride >= limit.
+ */
+#define SZS_WITHIN_MOST 65536u
+int szs_hip_within_fold(uint64_t const *cells, uint64_t cells_stride, uint32_t rows, uint32_t columns, uint64_t first_column,
+                        uint64_t self_first_row, uint64_t bound, int descending, uint32_t segments, uint32_t segment_columns,
+                        uint32_t *partials, uint64_t const *running, uint64_t *running_next, uint32_t limit, uint64_t *indices,
+                        uint64_t *scores, uint64_t stride, void *stream);
+int szs_hip_within_finish(uint64_t const *running, uint32_t const *partials, uint32_t segments, uint32_t rows, uint32_t limit,
+                          uint64_t *counts, uint64_t *indices, uint64_t *scores, uint64_t stride, void *stream);
+
+/**
  *  Equal dimensions of MinHash fingerprints (hip/fingerprint_matches.hip; host/fingerprint_search.c):
  *  cells[q][c] = #{ d < dimensions : queries[q][d] == candidates[c][d] } for q < rows, c < columns.  Both hash matrices are
  *  row-major u32 with a row stride in BYTES (a multiple of 4, at least 4 * dimensions), device-accessible.  Plain equality: two

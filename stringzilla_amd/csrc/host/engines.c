@@ -347,6 +347,35 @@ sz_status_t szs_rocm_top_k_u64tape(void *engine, szs_device_scope_t device, sz_s
     SZS_TOP_K_BODY(input_from_u64tape)
 }
 
+/* ---- within (host/within.c) ------------------------------------------------------------------------------------------- */
+
+#define SZS_WITHIN_BODY(MAKE_INPUT)                                                                                    \
+    if (limit > SZS_WITHIN_MOST || row_stride < limit || !queries)                                                     \
+        return szs_engine_within((szs_engine_s *)engine, (szs_scope_s *)device, NULL, NULL, bound, limit, counts,      \
+                                 indices, scores, row_stride, error_message);                                          \
+    szs_input_t const query_input = MAKE_INPUT(queries);                                                               \
+    szs_input_t candidate_input;                                                                                       \
+    if (candidates) candidate_input = MAKE_INPUT(candidates);                                                          \
+    return szs_engine_within((szs_engine_s *)engine, (szs_scope_s *)device, &query_input,                              \
+                             candidates ? &candidate_input : NULL, bound, limit, counts, indices, scores, row_stride,  \
+                             error_message);
+
+sz_status_t szs_rocm_within(void *engine, szs_device_scope_t device, sz_sequence_t const *queries, sz_sequence_t const *candidates,
+                            sz_ssize_t bound, sz_size_t limit, sz_size_t *counts, sz_size_t *indices, void *scores, sz_size_t row_stride,
+                            char const **error_message) {
+    SZS_WITHIN_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_within_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                    sz_sequence_u32tape_t const *candidates, sz_ssize_t bound, sz_size_t limit, sz_size_t *counts,
+                                    sz_size_t *indices, void *scores, sz_size_t row_stride, char const **error_message) {
+    SZS_WITHIN_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_within_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                    sz_sequence_u64tape_t const *candidates, sz_ssize_t bound, sz_size_t limit, sz_size_t *counts,
+                                    sz_size_t *indices, void *scores, sz_size_t row_stride, char const **error_message) {
+    SZS_WITHIN_BODY(input_from_u64tape)
+}
+
 /* ---- rerank (host/rerank.c) ------------------------------------------------------------------------------------------- */
 
 #define SZS_RERANK_BODY(MAKE_INPUT)                                                                                    \
@@ -490,6 +519,37 @@ sz_status_t szs_rocm_fuzzy_search_u64tape(void *engine, szs_device_scope_t devic
                                           sz_sequence_u64tape_t const *candidates, sz_size_t k, sz_size_t *indices, sz_size_t *distances,
                                           sz_size_t *starts, sz_size_t *ends, sz_size_t row_stride, char const **error_message) {
     SZS_FUZZY_SEARCH_BODY(input_from_u64tape)
+}
+
+#define SZS_FUZZY_SEARCH_WITHIN_BODY(MAKE_INPUT)                                                                       \
+    if (limit > SZS_WITHIN_MOST || row_stride < limit || !queries)                                                     \
+        return szs_engine_fuzzy_search_within((szs_engine_s *)engine, (szs_scope_s *)device, NULL, NULL, max_distance, \
+                                              limit, counts, indices, distances, starts, ends, row_stride,             \
+                                              error_message);                                                          \
+    szs_input_t const query_input = MAKE_INPUT(queries);                                                               \
+    szs_input_t candidate_input;                                                                                       \
+    if (candidates) candidate_input = MAKE_INPUT(candidates);                                                          \
+    return szs_engine_fuzzy_search_within((szs_engine_s *)engine, (szs_scope_s *)device, &query_input,                 \
+                                          candidates ? &candidate_input : NULL, max_distance, limit, counts, indices,  \
+                                          distances, starts, ends, row_stride, error_message);
+
+sz_status_t szs_rocm_fuzzy_search_within(void *engine, szs_device_scope_t device, sz_sequence_t const *queries,
+                                         sz_sequence_t const *candidates, sz_size_t max_distance, sz_size_t limit, sz_size_t *counts,
+                                         sz_size_t *indices, sz_size_t *distances, sz_size_t *starts, sz_size_t *ends,
+                                         sz_size_t row_stride, char const **error_message) {
+    SZS_FUZZY_SEARCH_WITHIN_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_fuzzy_search_within_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *queries,
+                                                 sz_sequence_u32tape_t const *candidates, sz_size_t max_distance, sz_size_t limit,
+                                                 sz_size_t *counts, sz_size_t *indices, sz_size_t *distances, sz_size_t *starts,
+                                                 sz_size_t *ends, sz_size_t row_stride, char const **error_message) {
+    SZS_FUZZY_SEARCH_WITHIN_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_fuzzy_search_within_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *queries,
+                                                 sz_sequence_u64tape_t const *candidates, sz_size_t max_distance, sz_size_t limit,
+                                                 sz_size_t *counts, sz_size_t *indices, sz_size_t *distances, sz_size_t *starts,
+                                                 sz_size_t *ends, sz_size_t row_stride, char const **error_message) {
+    SZS_FUZZY_SEARCH_WITHIN_BODY(input_from_u64tape)
 }
 
 /* ---- fuzzy scan (host/fuzzy_scan.c) ----------------------------------------------------------------------------------- */

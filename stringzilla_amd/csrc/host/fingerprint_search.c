@@ -188,7 +188,7 @@ sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scop
         }
         if (error == hipSuccess) error = szs_selection_emit(&selection, q0, rows);
     }
-    error = szs_selection_drain(&selection, error);
+    error = szs_selection_drain(selection.stream, error);
     if (error != hipSuccess) return szs_report_hip(error, error_message);
     return szs_report(sz_success_k, error_message, NULL);
 }

@@ -394,6 +394,14 @@ void szs_engine_follow_device(szs_engine_s *engine, int device);
 sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                              size_t k, size_t *indices, void *scores, size_t row_stride, char const **error_message);
 
+/* ---- within (within.c) -------------------------------------------------------------------------------------------------- */
+
+/** Every candidate inside `bound` per query: `counts` of `queries->count` cells, the leftmost `limit` hits a row in `indices` and
+ *  `scores` (`limit` 0: neither is looked at; `scores` may be NULL); `candidates` NULL: self-search.  Uses the engine's top-k buffers. */
+sz_status_t szs_engine_within(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                              sz_ssize_t bound, size_t limit, size_t *counts, size_t *indices, void *scores, size_t row_stride,
+                              char const **error_message);
+
 /* ---- rerank (rerank.c) -------------------------------------------------------------------------------------------------- */
 
 /** `candidates` NULL: the indices refer to the queries themselves (no index is excluded). */
@@ -428,6 +436,13 @@ sz_status_t szs_engine_alignments(szs_engine_s *engine, szs_scope_s *scope, szs_
 sz_status_t szs_engine_fuzzy_search(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                                     size_t k, size_t *indices, size_t *distances, size_t *starts, size_t *ends, size_t row_stride,
                                     char const **error_message);
+
+/** Every candidate whose fuzzy-find distance is at most `max_distance` per query: `counts`, and the leftmost `limit` hits a row in
+ *  `indices`, `distances` and - the winners pass - `ends` and `starts` (`limit` 0: none is looked at; `ends` needs `distances`,
+ *  `starts` needs `ends`).  Unit-cost byte Levenshtein engines only.  Uses the engine's top-k and rerank buffers. */
+sz_status_t szs_engine_fuzzy_search_within(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
+                                           size_t max_distance, size_t limit, size_t *counts, size_t *indices, size_t *distances,
+                                           size_t *starts, size_t *ends, size_t row_stride, char const **error_message);
 
 /* ---- fuzzy scan (fuzzy_scan.c) ------------------------------------------------------------------------------------------ */
 

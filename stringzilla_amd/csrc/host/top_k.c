@@ -7,44 +7,10 @@
  *  plans on the host while that fold runs, and its scoring launches queue behind it on the same stream.  After the last tile one
  *  launch writes the lists out, and one copy moves them to the caller's arrays when those are not device-accessible.  So every
  *  scoring tier serves top-k unchanged, and no knob changes a result: the lists only depend on the cells.  The budget and every
- *  step but the scoring are selection.c's (selection_internal.h), shared with the fingerprint and fuzzy searches.
+ *  step but the scoring are selection.c's (selection_internal.h), shared with the fingerprint and fuzzy searches; the sub-tapes of a
+ *  tile and the sums of its profile are there too, shared with within.c.
  */
 #include "selection_internal.h"
-
-#include <string.h>
-
-/* ---- sub-sequences: strings [first, first + count) of a side ------------------------------------------------------------- */
-
-typedef struct {
-    sz_sequence_t sequence; /* first member: the handle of the wrapper is the wrapper itself */
-    sz_sequence_t const *base;
-    size_t first;
-} szs_shifted_sequence_t;
-
-static sz_cptr_t shifted_start(void const *handle, sz_sorted_idx_t i) {
-    szs_shifted_sequence_t const *shifted = (szs_shifted_sequence_t const *)handle;
-    return shifted->base->get_start(shifted->base->handle, shifted->first + i);
-}
-static sz_size_t shifted_length(void const *handle, sz_sorted_idx_t i) {
-    szs_shifted_sequence_t const *shifted = (szs_shifted_sequence_t const *)handle;
-    return shifted->base->get_length(shifted->base->handle, shifted->first + i);
-}
-
-static szs_input_t slice_input(szs_input_t const *input, size_t first, size_t count, szs_shifted_sequence_t *wrapper) {
-    szs_input_t slice = *input;
-    slice.count = count;
-    if (input->kind == szs_input_sequence_k) {
-        wrapper->base = input->sequence, wrapper->first = first;
-        wrapper->sequence.handle = wrapper, wrapper->sequence.count = count;
-        wrapper->sequence.get_start = shifted_start, wrapper->sequence.get_length = shifted_length;
-        slice.sequence = &wrapper->sequence;
-    }
-    else
-        slice.offsets = (char const *)input->offsets + first * (input->kind == szs_input_u32tape_k ? 4 : 8);
-    return slice;
-}
-
-/* ---- the call ------------------------------------------------------------------------------------------------------------ */
 
 sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                              size_t k, size_t *indices, void *scores, size_t row_stride, char const **error_message) {
@@ -80,19 +46,14 @@ sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input
     for (size_t q0 = 0; q0 < q_count && status == sz_success_k && error == hipSuccess; q0 += block) {
         size_t const rows = q_count - q0 < block ? q_count - q0 : block;
         szs_shifted_sequence_t query_wrapper, candidate_wrapper;
-        szs_input_t const query_slice = slice_input(queries, q0, rows, &query_wrapper);
+        szs_input_t const query_slice = szs_slice_input(queries, q0, rows, &query_wrapper);
         error = szs_selection_block_begin(&selection, rows);
         for (size_t c0 = 0; c0 < c_count && error == hipSuccess; c0 += tile) {
             size_t const columns = c_count - c0 < tile ? c_count - c0 : tile;
-            szs_input_t const candidate_slice = slice_input(pool, c0, columns, &candidate_wrapper);
+            szs_input_t const candidate_slice = szs_slice_input(pool, c0, columns, &candidate_wrapper);
             status = szs_engine_cross(engine, scope, &query_slice, &candidate_slice, selection.cells, columns, error_message);
             if (status != sz_success_k) break;
-            szs_rocm_call_profile_t const *tile_profile = &engine->last_profile;
-            total.kernel_milliseconds += tile_profile->kernel_milliseconds, total.cells += tile_profile->cells;
-            total.pairs += tile_profile->pairs, total.algorithmic_bytes += tile_profile->algorithmic_bytes;
-            total.unique_bytes += tile_profile->unique_bytes, total.launches += tile_profile->launches;
-            if (tile_profile->longest_query > total.longest_query) total.longest_query = tile_profile->longest_query;
-            if (tile_profile->longest_candidate > total.longest_candidate) total.longest_candidate = tile_profile->longest_candidate;
+            szs_selection_profile_add(&total, &engine->last_profile);
             error = szs_selection_fold(&selection, q0, rows, c0, columns, self);
             total.launches += szs_selection_fold_launches(&selection);
         }
@@ -100,16 +61,9 @@ sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input
         error = szs_selection_emit(&selection, q0, rows);
         total.launches += 1;
     }
-    error = szs_selection_drain(&selection, error);
+    error = szs_selection_drain(selection.stream, error);
     if (status != sz_success_k) return status;
     if (error != hipSuccess) return szs_report_hip(error, error_message);
-    /* the profile of a top-k call: the last tile's, with the sums over all tiles (kernel time: the scoring launches) and the wall
-     * time of the whole call */
-    if (!c_count) memset(&engine->last_profile, 0, sizeof(engine->last_profile));
-    engine->last_profile.kernel_milliseconds = total.kernel_milliseconds, engine->last_profile.cells = total.cells;
-    engine->last_profile.pairs = total.pairs, engine->last_profile.algorithmic_bytes = total.algorithmic_bytes;
-    engine->last_profile.unique_bytes = total.unique_bytes, engine->last_profile.launches = total.launches;
-    engine->last_profile.longest_query = total.longest_query, engine->last_profile.longest_candidate = total.longest_candidate;
-    engine->last_profile.host_milliseconds = szs_now_milliseconds() - started;
+    szs_selection_profile_publish(engine, &total, c_count != 0, started);
     return szs_report(sz_success_k, error_message, NULL);
 }
