@@ -21,6 +21,9 @@
  *  - szs_rocm_within*           : EVERY candidate of every query inside a score bound - the full count and the leftmost `limit` hits
  *    in fixed (queries x limit) rows (csrc/host/within.c); szs_rocm_fuzzy_search_within* answers the same for approximate substring
  *    matches (csrc/host/fuzzy_search.c), and szs_rocm_within_probe reports how either call would be cut.
+ *  - szs_rocm_clusters*         : the connected components of those hits among ONE set of strings, a label per string - the groups of a
+ *    deduplication, from a lock-free union-find on the device (csrc/host/clusters.c); szs_rocm_fingerprint_clusters groups MinHash
+ *    fingerprints the same way, and szs_rocm_clusters_probe reports what a call would score.
  *  - szs_rocm_rerank*           : exact scores of LISTED candidates per query - what verifies the hits of a coarse search (top-k's own
  *    `indices`, a fingerprint search, any outside candidate generator) without a queries x candidates matrix (csrc/host/rerank.c).
  *  - szs_rocm_fuzzy_find*       : the best match of a query INSIDE each listed candidate - fewest edits to some substring, and where it
@@ -198,6 +201,63 @@ SZ_API_RUNTIME sz_status_t szs_rocm_within_u64tape(void *engine, szs_device_scop
  */
 SZ_API_RUNTIME sz_status_t szs_rocm_within_probe(sz_size_t queries_count, sz_size_t candidates_count, sz_size_t limit, sz_size_t *block,
                                                  sz_size_t *tile, sz_size_t *segments, sz_size_t *segment_columns);
+
+/**
+ *  CLUSTERS: the connected components of the graph "i ~ j iff the pair is a szs_rocm_within hit", as one label per string - the groups
+ *  a deduplication wants, where szs_rocm_within returns rows of neighbours that truncate at `limit`.  For n strings and a bound:
+ *      hit(i, j), i != j   = szs_rocm_within's predicate on the score of query i against candidate j: a DISTANCE engine hits iff
+ *                            bound >= 0 and score <= bound, compared unsigned; NW and SW hit iff the signed score >= bound;
+ *      i ~ j               iff hit(i, j) or hit(j, i): the graph is undirected;
+ *      labels[i]           = the SMALLEST index in the connected component of i, so labels[labels[i]] == labels[i]; a string with no
+ *                            neighbour labels itself; duplicates of one string are ordinary hits (distance 0) and share a component;
+ *      *clusters_count     = the number of i with labels[i] == i (`clusters_count` may be NULL).
+ *  The result is a function of the strings, the engine and the bound alone: no knob, tile size or arrival order changes a byte -
+ *  atomics build the forest, the minimum-index label is what makes their order invisible.  A negative bound on a distance engine
+ *  gives labels 0 .. n-1, and nothing is scored.  n == 0 succeeds with nothing written except *clusters_count = 0.
+ *
+ *  `engine`: any engine szs_rocm_within takes.  `labels`: n 8-byte cells in host, pinned, unified or device memory; plain host memory
+ *  is staged - n x 8 bytes, not data-dependent.  Refused before anything is launched, with nothing written, in this order: more than
+ *  2^32 - 1 strings (sz_unexpected_dimensions_k; a choice, not a measurement - the forest is 32-bit words, and the square of that
+ *  count is beyond any call); an engine that is none of the above; NULL strings; with n > 0 NULL `labels` (each sz_status_unknown_k).
+ *  Synchronous, also when it fails.
+ *
+ *  The call scores szs_rocm_within's self-form tiles (ordinary engine calls into device scratch) and folds each with
+ *  csrc/hip/clusters.hip: a lock-free union-find over n 32-bit parents, hooking the larger root under the smaller.  Where the engine
+ *  is symmetric in its two sides - every Levenshtein engine; NW and SW iff their substitution table is symmetric over the classes in
+ *  use - the tiles of a block of rows start at the block's own first string, so every pair i < j is scored once; otherwise the whole
+ *  square is scored.  The `top_k_tile` knob caps the columns of a tile.  szs_rocm_last_call_profile: pairs and cells are the sums
+ *  over the scoring launches, so the triangle shows there; launches = scoring, begin, union and finish launches; kernel time = the
+ *  scoring launches.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_clusters(void *engine, szs_device_scope_t device, sz_sequence_t const *strings, sz_ssize_t bound,
+                                             sz_size_t *labels, sz_size_t *clusters_count, char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_clusters_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *strings,
+                                                     sz_ssize_t bound, sz_size_t *labels, sz_size_t *clusters_count,
+                                                     char const **error_message);
+SZ_API_RUNTIME sz_status_t szs_rocm_clusters_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *strings,
+                                                     sz_ssize_t bound, sz_size_t *labels, sz_size_t *clusters_count,
+                                                     char const **error_message);
+
+/**
+ *  The same components over MinHash fingerprints: rows i != j of an (n x dimensions) hash matrix hit iff at least `min_matches` of
+ *  their dimensions are equal (szs_rocm_fingerprint_matches' count).  `hashes_stride` in bytes, as for szs_rocm_fingerprint_top_k;
+ *  hashes in plain host memory are staged tile by tile.  min_matches == 0 makes every pair a hit - one cluster; min_matches beyond
+ *  the dimensions none, and nothing is scored.  Refused in this order: more than 2^32 - 1 rows; a stride that is no multiple of 4, an
+ *  engine that is no fingerprints engine, a stride below 4 x dimensions; then - n == 0 succeeds as above - NULL `hashes`, NULL `labels`.
+ *  Matches are symmetric: always the triangle.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_fingerprint_clusters(void *engine, szs_device_scope_t device, sz_u32_t const *hashes,
+                                                         sz_size_t hashes_stride, sz_size_t count, sz_size_t min_matches,
+                                                         sz_size_t *labels, sz_size_t *clusters_count, char const **error_message);
+
+/**
+ *  How szs_rocm_clusters would cut a call over `count` strings - host only, no GPU: the rows of a block, the columns of a tile, and
+ *  the tiles and pairs it would score - with `symmetric` the triangle (per block of rows, rows x (count - first row of the block)),
+ *  otherwise the square.  The `top_k_tile` knob applies as it does to the call.  Outputs are optional.  count > 2^32 - 1:
+ *  sz_unexpected_dimensions_k.
+ */
+SZ_API_RUNTIME sz_status_t szs_rocm_clusters_probe(sz_size_t count, int symmetric, sz_size_t *block, sz_size_t *tile,
+                                                   sz_size_t *tiles_scored, sz_size_t *pairs_scored);
 
 /**
  *  Rerank: the exact scores of the candidates an index row LISTS per query, in one call -

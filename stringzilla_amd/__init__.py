@@ -246,6 +246,29 @@ def _listed_cells(matrix, name, shape_wanted):
     return pointer, strides[0] if shape[0] > 1 else shape[1], shape
 
 
+def _label_cells(out, rows, gpu_device):
+    """The `out` of a `clusters` call - a contiguous vector of `rows` 8-byte cells, a NumPy array or a torch tensor on the host or on the
+    call's GPU - or, `out` None, a fresh device vector -> (what holds the labels, pointer); ValueError otherwise."""
+    import torch
+
+    if out is None:
+        labels = torch.empty(max(rows, 1), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+        return labels, labels.data_ptr()
+    if isinstance(out, np.ndarray):
+        shape, itemsize, unit, pointer = out.shape, out.dtype.itemsize, out.strides == (8,), out.ctypes.data
+    elif type(out).__module__.partition(".")[0] == "torch" and hasattr(out, "data_ptr"):
+        shape, itemsize, unit, pointer = tuple(out.shape), out.element_size(), out.stride() == (1,), out.data_ptr()
+    else:
+        raise ValueError(f"`out` must be a NumPy array or a torch tensor, got {type(out).__name__}")
+    if shape != (rows,) or itemsize != 8 or (rows > 1 and not unit):
+        raise ValueError(f"`out` must be a contiguous vector of {rows} 8-byte cells")
+    if getattr(out, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
+        if out.device.index != gpu_device:
+            raise ValueError(f"`out` is on {out.device}, the call runs on GPU {gpu_device}")
+        torch.cuda.current_stream(out.device).synchronize()  # torch's own stream may still be filling it
+    return out, pointer
+
+
 class _Engine:
     """Shared call path: `engine(queries, candidates=None, device=None, out=None)` (README.md:472-482)."""
 
@@ -679,6 +702,28 @@ class _Engine:
             raise ValueError(f"max_distance must be a non-negative integer below 2**64, got {max_distance!r}")
         names = ("indices", "distances", "starts", "ends") if starts else ("indices", "distances", "ends")
         return self._bounded_rows("szs_rocm_fuzzy_search_within", names, (), queries, candidates, int(max_distance), limit, device, out)
+
+    def clusters(self, strings, bound, device: Optional[DeviceScope] = None, out=None):
+        """The connected components of the graph "i ~ j iff the pair is a `within` hit" (`szs_rocm_clusters_*`): returns
+        `(labels, count)` - a `uint64` NumPy vector of `len(strings)` and an `int`.  `hit(i, j)` is `within`'s predicate on the score of
+        string `i` against string `j` - a distance engine hits iff `bound >= 0` and `score <= bound`, NW / SW iff the signed
+        `score >= bound` - and the graph is undirected: either direction joins the two.  `labels[i]` is the smallest index of the
+        component of `i`, so `labels[labels[i]] == labels[i]` and a string with no neighbour labels itself; `count` is the number of
+        components.  Nothing truncates - there is no `limit` - and no knob or tile size changes a byte.  `out`: a contiguous NumPy
+        vector or torch tensor of `len(strings)` 8-byte cells, host or device, filled and returned in place of `labels`."""
+        if isinstance(bound, (bool, np.bool_)) or not isinstance(bound, (int, np.integer)) or not -2**63 <= int(bound) < 2**63:
+            raise ValueError(f"bound must be an integer of 64 signed bits, got {bound!r}")
+        strings = _as_strs(strings)
+        rows = len(strings)
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        labels, pointer = _label_cells(out, rows, gpu_device)
+        error, count = ctypes.c_char_p(), ctypes.c_size_t(0)
+        call = lib.szs_rocm_clusters_u64tape if strings.wide_offsets else lib.szs_rocm_clusters_u32tape
+        tape = strings._tape(gpu_device)
+        status = call(self.handle, scope.handle, ctypes.byref(tape), int(bound), pointer, ctypes.byref(count), ctypes.byref(error))
+        _abi.check(status, error)
+        return (labels[:rows].cpu().numpy().view(np.uint64) if out is None else out), int(count.value)
 
     def _bounded_rows(self, entry, names, optional, queries, candidates, bound, limit, device, out):
         """What `within` and `fuzzy_search_within` share: the checks, a vector of counts and `len(names)` matrices of `limit` slots a
@@ -1164,6 +1209,26 @@ class Fingerprints:
             return out
         host = both[:, :rows].cpu().numpy().view(np.uint64)
         return host[0], host[1]
+
+    def clusters(self, hashes, min_matches, device: Optional[DeviceScope] = None, out=None):
+        """The connected components of "rows `i` and `j` share at least `min_matches` equal dimensions"
+        (`szs_rocm_fingerprint_clusters`): returns `(labels, count)` as the similarity engines' `clusters` does - `labels[i]` the
+        smallest row of the component of row `i`, a `uint64` NumPy vector, and the number of components.  `hashes` as `top_k` takes
+        them.  `min_matches=0` makes every pair a hit - one cluster; beyond `ndim` none.  `out`: a contiguous NumPy vector or torch
+        tensor of 8-byte cells, host or device, filled and returned in place of `labels`."""
+        if isinstance(min_matches, (bool, np.bool_)) or not isinstance(min_matches, (int, np.integer)) or not 0 <= int(min_matches) < 2**64:
+            raise ValueError(f"min_matches must be a non-negative integer below 2**64, got {min_matches!r}")
+        side = self._hashes(hashes, "hashes")
+        scope = device or self._scope or _get_default_scope()
+        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        rows = side[2]
+        self._drain_torch(gpu_device, side)
+        labels, pointer = _label_cells(out, rows, gpu_device)
+        message, count = ctypes.c_char_p(), ctypes.c_size_t(0)
+        status = lib.szs_rocm_fingerprint_clusters(self.handle, scope.handle, side[0], side[1], rows, int(min_matches), pointer,
+                                                   ctypes.byref(count), ctypes.byref(message))
+        _abi.check(status, message)
+        return (labels[:rows].cpu().numpy().view(np.uint64) if out is None else out), int(count.value)
 
     def __del__(self):
         handle = getattr(self, "handle", None)

@@ -87,6 +87,7 @@ _FUZZY_FIND = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_
 _FUZZY_FIND_SPANS = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 _FUZZY_SEARCH = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
 _WITHIN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_ssize_t, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, ERR])
+_CLUSTERS = (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_ssize_t, c_void_p, c_void_p, ERR])
 _FUZZY_SEARCH_WITHIN = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_size_t, ERR])
 _FUZZY_SCAN = (c_int,[c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ERR])
@@ -151,6 +152,10 @@ SIGNATURES = {
     "szs_rocm_within": _WITHIN, "szs_rocm_within_u32tape": _WITHIN, "szs_rocm_within_u64tape": _WITHIN,
     "szs_rocm_within_probe": (c_int, [c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
                                       ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "szs_rocm_clusters": _CLUSTERS, "szs_rocm_clusters_u32tape": _CLUSTERS, "szs_rocm_clusters_u64tape": _CLUSTERS,
+    "szs_rocm_fingerprint_clusters": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, ERR]),
+    "szs_rocm_clusters_probe": (c_int, [c_size_t, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                        ctypes.POINTER(c_size_t)]),
     "szs_rocm_fuzzy_search_within": _FUZZY_SEARCH_WITHIN, "szs_rocm_fuzzy_search_within_u32tape": _FUZZY_SEARCH_WITHIN,
     "szs_rocm_fuzzy_search_within_u64tape": _FUZZY_SEARCH_WITHIN,
     "szs_rocm_rerank": _RERANK, "szs_rocm_rerank_u32tape": _RERANK, "szs_rocm_rerank_u64tape": _RERANK,
@@ -272,6 +277,18 @@ def within_probe(queries_count, candidates_count, limit):
     if status != 0:
         raise StringZillasError(status, None)
     return int(block.value), int(tile.value), int(segments.value), int(segment_columns.value)
+
+
+def clusters_probe(count, symmetric):
+    """`szs_rocm_clusters_probe`: what `clusters` would score over `count` strings - no GPU involved.  Returns (block, tile,
+    tiles_scored, pairs_scored): the rows of a block, the columns of a tile, and the tiles and pairs of the triangle (`symmetric`) or of
+    the whole square.  The `top_k_tile` knob applies as it does to the call."""
+    block, tile, tiles, pairs = c_size_t(0), c_size_t(0), c_size_t(0), c_size_t(0)
+    status = lib.szs_rocm_clusters_probe(count, 1 if symmetric else 0, ctypes.byref(block), ctypes.byref(tile), ctypes.byref(tiles),
+                                         ctypes.byref(pairs))
+    if status != 0:
+        raise StringZillasError(status, None)
+    return int(block.value), int(tile.value), int(tiles.value), int(pairs.value)
 
 
 def fuzzy_scan_probe(queries_count, longest_query, text_length):

@@ -276,6 +276,23 @@ int szs_hip_within_finish(uint64_t const *running, uint32_t const *partials, uin
                           uint64_t *counts, uint64_t *indices, uint64_t *scores, uint64_t stride, void *stream);
 
 /**
+ *  Connected components inside a score bound, over the same scored tiles (hip/clusters.hip; host/selection.c; DESIGN.md section
+ *  4.16): ONE forest `parent` of `count` 32-bit words for a whole call, in which every value ever stored to parent[x] is <= x.
+ *
+ *  szs_hip_clusters_begin makes every string a root.  szs_hip_clusters_union joins row r's string first_row + r with column c's
+ *  string first_column + c of the tile `cells[r * cells_stride + c]` wherever the cell hits - szs_hip_within_fold's compare and grid,
+ *  `segments` workgroups a row with segments * segment_columns >= columns - and the two are different strings; first_row + rows and
+ *  first_column + columns must not exceed `count`.  Tiles may arrive in any order and cover any part of the square: the forest after
+ *  the last one depends on the set of hits alone.  szs_hip_clusters_finish writes labels[i] = the root of i - the smallest index of
+ *  its component - and ADDS the number of roots to the 8-byte word `clusters_count`, which the caller zeroes.
+ */
+int szs_hip_clusters_begin(uint32_t *parent, uint32_t count, void *stream);
+int szs_hip_clusters_union(uint64_t const *cells, uint64_t cells_stride, uint32_t rows, uint32_t columns, uint64_t first_row,
+                           uint64_t first_column, uint64_t bound, int descending, uint32_t segments, uint32_t segment_columns,
+                           uint32_t *parent, uint32_t count, void *stream);
+int szs_hip_clusters_finish(uint32_t const *parent, uint32_t count, uint64_t *labels, uint64_t *clusters_count, void *stream);
+
+/**
  *  Equal dimensions of MinHash fingerprints (hip/fingerprint_matches.hip; host/fingerprint_search.c):
  *  cells[q][c] = #{ d < dimensions : queries[q][d] == candidates[c][d] } for q < rows, c < columns.  Both hash matrices are
  *  row-major u32 with a row stride in BYTES (a multiple of 4, at least 4 * dimensions), device-accessible.  Plain equality: two

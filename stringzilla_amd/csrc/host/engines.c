@@ -376,6 +376,27 @@ sz_status_t szs_rocm_within_u64tape(void *engine, szs_device_scope_t device, sz_
     SZS_WITHIN_BODY(input_from_u64tape)
 }
 
+/* ---- clusters (host/clusters.c) --------------------------------------------------------------------------------------- */
+
+#define SZS_CLUSTERS_BODY(MAKE_INPUT)                                                                                  \
+    szs_input_t input;                                                                                                 \
+    if (strings) input = MAKE_INPUT(strings);                                                                          \
+    return szs_engine_clusters((szs_engine_s *)engine, (szs_scope_s *)device, strings ? &input : NULL, bound, labels,  \
+                               clusters_count, error_message);
+
+sz_status_t szs_rocm_clusters(void *engine, szs_device_scope_t device, sz_sequence_t const *strings, sz_ssize_t bound, sz_size_t *labels,
+                              sz_size_t *clusters_count, char const **error_message) {
+    SZS_CLUSTERS_BODY(input_from_sequence)
+}
+sz_status_t szs_rocm_clusters_u32tape(void *engine, szs_device_scope_t device, sz_sequence_u32tape_t const *strings, sz_ssize_t bound,
+                                      sz_size_t *labels, sz_size_t *clusters_count, char const **error_message) {
+    SZS_CLUSTERS_BODY(input_from_u32tape)
+}
+sz_status_t szs_rocm_clusters_u64tape(void *engine, szs_device_scope_t device, sz_sequence_u64tape_t const *strings, sz_ssize_t bound,
+                                      sz_size_t *labels, sz_size_t *clusters_count, char const **error_message) {
+    SZS_CLUSTERS_BODY(input_from_u64tape)
+}
+
 /* ---- rerank (host/rerank.c) ------------------------------------------------------------------------------------------- */
 
 #define SZS_RERANK_BODY(MAKE_INPUT)                                                                                    \
@@ -661,4 +682,10 @@ sz_status_t szs_rocm_fingerprint_top_k(szs_fingerprints_t engine, szs_device_sco
     return szs_fingerprints_top_k((szs_fingerprints_s *)engine, (szs_scope_s *)device, query_hashes, query_hashes_stride, queries_count,
                                   candidate_hashes, candidate_hashes_stride, candidates_count, k, indices, matches, row_stride,
                                   error_message);
+}
+sz_status_t szs_rocm_fingerprint_clusters(void *engine, szs_device_scope_t device, sz_u32_t const *hashes, sz_size_t hashes_stride,
+                                          sz_size_t count, sz_size_t min_matches, sz_size_t *labels, sz_size_t *clusters_count,
+                                          char const **error_message) {
+    return szs_fingerprints_clusters((szs_fingerprints_s *)engine, (szs_scope_s *)device, hashes, hashes_stride, count, min_matches, labels,
+                                     clusters_count, error_message);
 }

@@ -1,7 +1,8 @@
 /*
  *  fingerprint_search.c - what MinHash fingerprints are for: the equal dimensions of every (query, candidate) pair
  *  (szs_rocm_fingerprint_matches) and the k candidates with the most of them per query (szs_rocm_fingerprint_top_k);
- *  include/stringzillas/stringzillas_rocm.h, DESIGN.md section 4.7.
+ *  include/stringzillas/stringzillas_rocm.h, DESIGN.md section 4.7.  szs_rocm_fingerprint_clusters, at the end, is the search's
+ *  loop over ONE side with the forest fold of hip/clusters.hip behind its tiles.
  *
  *  Both calls are cut into blocks of queries x tiles of candidates.  hip/fingerprint_matches.hip counts a tile; the matrix call
  *  writes it where the caller wants it, the search writes 8-byte cells into a device scratch matrix that hip/top_k.hip folds into
@@ -190,5 +191,64 @@ sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scop
     }
     error = szs_selection_drain(selection.stream, error);
     if (error != hipSuccess) return szs_report_hip(error, error_message);
+    return szs_report(sz_success_k, error_message, NULL);
+}
+
+sz_status_t szs_fingerprints_clusters(szs_fingerprints_s *engine, szs_scope_s *scope, sz_u32_t const *hashes, sz_size_t hashes_stride,
+                                      sz_size_t count, sz_size_t min_matches, sz_size_t *labels, sz_size_t *clusters_count,
+                                      char const **error_message) {
+    if (count > SZS_CLUSTERS_MOST_STRINGS)
+        return szs_report(sz_unexpected_dimensions_k, error_message, "At most 2^32 - 1 fingerprints: the forest is 32-bit words");
+    sz_status_t status = vet(engine, hashes_stride, NULL, 0, error_message);
+    if (status != sz_success_k) return status;
+    if (!count) {
+        if (clusters_count) *clusters_count = 0;
+        return szs_report(sz_success_k, error_message, NULL);
+    }
+    if (!hashes) return szs_report(sz_status_unknown_k, error_message, "Hashes must not be null");
+    if (!labels) return szs_report(sz_status_unknown_k, error_message, "Labels must not be null");
+
+    int device = 0;
+    hipStream_t stream = NULL;
+    status = szs_scope_bind_gpu(scope, &device, &stream, error_message);
+    if (status != sz_success_k) return status;
+    szs_fingerprints_follow_device(engine, device);
+
+    uint32_t const dimensions = engine->dimensions;
+    size_t const row_bytes = (size_t)dimensions * sizeof(uint32_t);
+    int const reachable = min_matches <= dimensions; /* no pair shares more dimensions than there are: nothing is scored */
+    szs_hash_side_t rows_side = {(char const *)hashes, hashes_stride, count, szs_classify_pointer(hashes).device_accessible, NULL};
+    szs_hash_side_t columns_side = rows_side;
+
+    /* the shared budget, within the staging areas of hashes the device cannot read; matches are symmetric: always the triangle */
+    size_t const most_staged = rows_side.device_accessible ? SIZE_MAX : at_least_one(SZS_SEARCH_STAGE_BYTES / row_bytes);
+    szs_selection_clusters_t selection = {.stream = stream, .device = device, .descending = 1 /* at least min_matches */,
+                                          .bound = (uint64_t)min_matches, .count = count, .labels = (uint64_t *)labels,
+                                          .plan = szs_selection_clusters_plan(count, most_staged, most_staged)};
+    size_t const block = selection.plan.cut.block, tile = selection.plan.cut.tile;
+    status = reserve_staging(engine, device, &rows_side, block, &columns_side, tile, row_bytes, error_message);
+    if (status == sz_success_k) status = szs_selection_clusters_reserve(&selection, &engine->selection, error_message);
+    if (status != sz_success_k) return status;
+
+    uint64_t roots = 0;
+    hipError_t error = szs_selection_clusters_begin(&selection);
+    for (size_t q0 = 0; q0 < count && reachable && error == hipSuccess; q0 += block) {
+        size_t const rows = at_most(count - q0, block);
+        uint32_t const *row_hashes = NULL, *column_hashes = NULL;
+        uint64_t row_stride = 0, column_stride = 0;
+        error = side_rows(&rows_side, q0, rows, row_bytes, stream, &row_hashes, &row_stride);
+        for (size_t c0 = q0; c0 < count && error == hipSuccess; c0 += tile) {
+            size_t const columns = at_most(count - c0, tile);
+            error = side_rows(&columns_side, c0, columns, row_bytes, stream, &column_hashes, &column_stride);
+            if (error == hipSuccess)
+                error = (hipError_t)szs_hip_fingerprint_matches_u64(row_hashes, row_stride, (uint32_t)rows, column_hashes, column_stride,
+                                                                    (uint32_t)columns, dimensions, selection.cells, columns, stream);
+            if (error == hipSuccess) error = szs_selection_clusters_fold(&selection, q0, rows, c0, columns);
+        }
+    }
+    if (error == hipSuccess) error = szs_selection_clusters_finish(&selection, &roots);
+    error = szs_selection_drain(selection.stream, error);
+    if (error != hipSuccess) return szs_report_hip(error, error_message);
+    if (clusters_count) *clusters_count = (size_t)roots;
     return szs_report(sz_success_k, error_message, NULL);
 }

@@ -30,13 +30,30 @@ szs_selection_plan_t szs_selection_plan(size_t q_count, size_t c_count, size_t k
     return selection_cut(q_count, c_count, SZS_SELECTION_LIST_BYTES / list_bytes, most_block_rows, most_tile_rows);
 }
 
-szs_selection_within_plan_t szs_selection_within_plan(size_t q_count, size_t c_count, size_t limit) {
-    size_t const staged_row_bytes = 2 * limit * sizeof(uint64_t); /* indices and scores */
-    szs_selection_plan_t cut = selection_cut(q_count, c_count, limit ? SZS_SELECTION_LIST_BYTES / staged_row_bytes : SIZE_MAX, SIZE_MAX, SIZE_MAX);
+/** The segments of hip/within.hip's grid over `cut`: of a whole number of rounds, and as many as cover a full tile. */
+static szs_selection_within_plan_t within_segments(szs_selection_plan_t cut) {
     size_t segment_columns = (cut.tile + cut.segments - 1) / cut.segments;
     segment_columns = (segment_columns + SZS_SELECTION_SEGMENT_QUANTUM - 1) / SZS_SELECTION_SEGMENT_QUANTUM * SZS_SELECTION_SEGMENT_QUANTUM;
     cut.segments = (cut.tile + segment_columns - 1) / segment_columns;
     return (szs_selection_within_plan_t){cut, segment_columns};
+}
+
+szs_selection_within_plan_t szs_selection_within_plan(size_t q_count, size_t c_count, size_t limit) {
+    size_t const staged_row_bytes = 2 * limit * sizeof(uint64_t); /* indices and scores */
+    return within_segments(selection_cut(q_count, c_count, limit ? SZS_SELECTION_LIST_BYTES / staged_row_bytes : SIZE_MAX, SIZE_MAX, SIZE_MAX));
+}
+
+szs_selection_within_plan_t szs_selection_clusters_plan(size_t count, size_t most_block_rows, size_t most_tile_rows) {
+    return within_segments(selection_cut(count ? count : 1, count, SIZE_MAX, most_block_rows, most_tile_rows));
+}
+
+void szs_selection_clusters_work(szs_selection_within_plan_t const *plan, size_t count, int symmetric, size_t *tiles, size_t *pairs) {
+    size_t const block = plan->cut.block, tile = plan->cut.tile;
+    *tiles = *pairs = 0;
+    for (size_t q0 = 0; q0 < count; q0 += block) {
+        size_t const rows = at_most(count - q0, block), columns = symmetric ? count - q0 : count;
+        *tiles += (columns + tile - 1) / tile, *pairs += rows * columns;
+    }
 }
 
 void szs_selection_release(szs_selection_buffers_t *buffers) {
@@ -194,5 +211,42 @@ hipError_t szs_selection_within_finish(szs_selection_within_t *call, size_t q0, 
     if (error == hipSuccess && !call->direct && scores)
         error = hipMemcpy2DAsync(call->scores + q0 * row_stride, row_stride * sizeof(uint64_t), scores, limit * sizeof(uint64_t),
                                  limit * sizeof(uint64_t), rows, hipMemcpyDefault, call->stream);
+    return error;
+}
+
+/* ---- the forest fold (hip/clusters.hip) --------------------------------------------------------------------------------------- */
+
+sz_status_t szs_selection_clusters_reserve(szs_selection_clusters_t *call, szs_selection_buffers_t *buffers, char const **error_message) {
+    size_t const count = call->count;
+    /* labels a kernel can write go straight there; others (plain host memory) are staged and copied in one piece */
+    call->direct = szs_classify_pointer(call->labels).device_accessible;
+    sz_status_t status = szs_buffer_reserve(&buffers->scratch, szs_memory_device_k, call->device,
+                                            call->plan.cut.block * call->plan.cut.tile * sizeof(uint64_t), error_message);
+    if (status == sz_success_k)
+        status = szs_buffer_reserve(&buffers->lists, szs_memory_device_k, call->device, sizeof(uint64_t) + count * sizeof(uint32_t), error_message);
+    if (status == sz_success_k && !call->direct)
+        status = szs_buffer_reserve(&buffers->out, szs_memory_device_k, call->device, count * sizeof(uint64_t), error_message);
+    call->cells = (uint64_t *)buffers->scratch.pointer, call->roots = (uint64_t *)buffers->lists.pointer;
+    call->parent = (uint32_t *)(call->roots + 1), call->staged = (uint64_t *)buffers->out.pointer;
+    return status;
+}
+
+hipError_t szs_selection_clusters_begin(szs_selection_clusters_t const *call) {
+    hipError_t const error = hipMemsetAsync(call->roots, 0, sizeof(uint64_t), call->stream);
+    return error != hipSuccess ? error : (hipError_t)szs_hip_clusters_begin(call->parent, (uint32_t)call->count, call->stream);
+}
+
+hipError_t szs_selection_clusters_fold(szs_selection_clusters_t const *call, size_t q0, size_t rows, size_t c0, size_t columns) {
+    return (hipError_t)szs_hip_clusters_union(call->cells, columns, (uint32_t)rows, (uint32_t)columns, q0, c0, call->bound, call->descending,
+                                              (uint32_t)call->plan.cut.segments, (uint32_t)call->plan.segment_columns, call->parent,
+                                              (uint32_t)call->count, call->stream);
+}
+
+hipError_t szs_selection_clusters_finish(szs_selection_clusters_t const *call, uint64_t *clusters_count) {
+    uint64_t *const labels = call->direct ? call->labels : call->staged;
+    hipError_t error = (hipError_t)szs_hip_clusters_finish(call->parent, (uint32_t)call->count, labels, call->roots, call->stream);
+    if (error == hipSuccess && !call->direct)
+        error = hipMemcpyAsync(call->labels, labels, call->count * sizeof(uint64_t), hipMemcpyDefault, call->stream);
+    if (error == hipSuccess) error = hipMemcpyAsync(clusters_count, call->roots, sizeof(uint64_t), hipMemcpyDeviceToHost, call->stream);
     return error;
 }

@@ -5,7 +5,9 @@
  *  block, fold a tile, emit a block, drain.  Policy stays with the callers: the checks, the loops, how a tile is scored, the profile.
  *  Every step enqueues on the call's stream and returns; only the drain waits.  The calls that keep EVERY candidate inside a bound
  *  (within.c: szs_rocm_within*; fuzzy_search.c: szs_rocm_fuzzy_search_within*) share the budget, the buffers
- *  and the drain, and have steps of their own around hip/within.hip below.
+ *  and the drain, and have steps of their own around hip/within.hip below; so do the calls that group ONE set of strings by those
+ *  hits (clusters.c: szs_rocm_clusters*; fingerprint_search.c: szs_rocm_fingerprint_clusters), around
+ *  hip/clusters.hip.
  */
 #ifndef SZS_SELECTION_INTERNAL_H_
 #define SZS_SELECTION_INTERNAL_H_
@@ -124,5 +126,43 @@ static inline unsigned szs_selection_within_fold_launches(szs_selection_within_t
 /** Rows [q0, q0 + rows) of the caller's counts, and the empty pairs behind the hits of every row: one launch, and one copy per
  *  staged array. */
 hipError_t szs_selection_within_finish(szs_selection_within_t *call, size_t q0, size_t rows);
+
+/* ---- the third fold: the connected components of the hits (hip/clusters.hip; clusters.c: szs_rocm_clusters*; fingerprint_search.c:
+ *      szs_rocm_fingerprint_clusters).  The same tiles - both sides the SAME strings -, buffers and drain; no
+ *      rows and no counts - one forest of `count` 32-bit parents for the whole call, and a label a string behind the last tile. ---- */
+
+#define SZS_CLUSTERS_MOST_STRINGS ((size_t)0xFFFFFFFFu) /* the forest is 32-bit words: a choice, not a measurement */
+
+/** The budget of a call over `count` strings: szs_selection_within_plan(count, count, 0) within the caller's caps (SIZE_MAX: none). */
+szs_selection_within_plan_t szs_selection_clusters_plan(size_t count, size_t most_block_rows, size_t most_tile_rows);
+
+/** What a call over `count` strings scores, cut as `plan` cuts it: with `symmetric` the tiles of a block of rows start at the
+ *  block's own first string - every pair i < j once, as (row i, column j), plus the block's own square below the diagonal -
+ *  otherwise at 0, the whole square. */
+void szs_selection_clusters_work(szs_selection_within_plan_t const *plan, size_t count, int symmetric, size_t *tiles, size_t *pairs);
+
+/** One call: the caller fills the first group, szs_selection_clusters_reserve the second. */
+typedef struct {
+    hipStream_t stream;
+    int device, descending;
+    uint64_t bound; /* as the kernel compares it */
+    size_t count;
+    szs_selection_within_plan_t plan;
+    uint64_t *labels; /* the caller's: `count` cells */
+
+    int direct; /* the finish kernel writes the caller's labels itself */
+    uint64_t *cells, *roots, *staged;
+    uint32_t *parent;
+} szs_selection_clusters_t;
+
+/** Reserves a block x tile of cells, the forest - 4 bytes a string - with the 8-byte count of its roots, and - for labels a kernel
+ *  cannot write (plain host memory) - 8 bytes a string of staging. */
+sz_status_t szs_selection_clusters_reserve(szs_selection_clusters_t *call, szs_selection_buffers_t *buffers, char const **error_message);
+/** Every string a root, no root counted: one launch. */
+hipError_t szs_selection_clusters_begin(szs_selection_clusters_t const *call);
+/** Joins the strings of every hit of the scored tile `cells[r * columns + c]` - strings q0 + r and c0 + c: one launch. */
+hipError_t szs_selection_clusters_fold(szs_selection_clusters_t const *call, size_t q0, size_t rows, size_t c0, size_t columns);
+/** The caller's labels and `*clusters_count`, a word the HOST can write: one launch, and a copy for each. */
+hipError_t szs_selection_clusters_finish(szs_selection_clusters_t const *call, uint64_t *clusters_count);
 
 #endif /* SZS_SELECTION_INTERNAL_H_ */

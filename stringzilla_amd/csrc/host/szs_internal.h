@@ -258,6 +258,10 @@ sz_status_t szs_fingerprints_top_k(szs_fingerprints_s *engine, szs_scope_s *scop
                                    sz_size_t query_hashes_stride, sz_size_t queries_count, sz_u32_t const *candidate_hashes,
                                    sz_size_t candidate_hashes_stride, sz_size_t candidates_count, sz_size_t k, sz_size_t *indices,
                                    sz_size_t *matches, sz_size_t row_stride, char const **error_message);
+/** The connected components of "rows i and j share at least `min_matches` dimensions": szs_engine_clusters' outputs. */
+sz_status_t szs_fingerprints_clusters(szs_fingerprints_s *engine, szs_scope_s *scope, sz_u32_t const *hashes, sz_size_t hashes_stride,
+                                      sz_size_t count, sz_size_t min_matches, sz_size_t *labels, sz_size_t *clusters_count,
+                                      char const **error_message);
 
 /* ---- planner (plan.c) - pure host logic, unit-tested without a GPU through the szs_rocm_plan_* exports ------------ */
 
@@ -401,6 +405,13 @@ sz_status_t szs_engine_top_k(szs_engine_s *engine, szs_scope_s *scope, szs_input
 sz_status_t szs_engine_within(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *queries, szs_input_t const *candidates,
                               sz_ssize_t bound, size_t limit, size_t *counts, size_t *indices, void *scores, size_t row_stride,
                               char const **error_message);
+
+/* ---- clusters (clusters.c) ---------------------------------------------------------------------------------------------- */
+
+/** The connected components of "i ~ j iff hit(i, j) or hit(j, i)", `within`'s hit: `labels` of `strings->count` cells, each the
+ *  smallest index of its string's component; `clusters_count` (optional, a host word) their number.  Uses the engine's top-k buffers. */
+sz_status_t szs_engine_clusters(szs_engine_s *engine, szs_scope_s *scope, szs_input_t const *strings, sz_ssize_t bound, size_t *labels,
+                                size_t *clusters_count, char const **error_message);
 
 /* ---- rerank (rerank.c) -------------------------------------------------------------------------------------------------- */
 
