@@ -619,7 +619,8 @@ def test_systolic_known_answers_and_golden_matrices(gpu, golden):
 @pytest.mark.parametrize("gaps", [(-4, -4), (-4, -1), (-11, -2), (2, -1)])
 def test_systolic_alignment_fuzz(gpu, oracle, kind, gaps):
     """Band edges (512 rows per wavefront), lane edges (8 rows per lane), the 64-column hand-over chunks, empties, more
-    candidates than lanes, asymmetric tables; local alignment with a positive gap cost takes the non-saturating form."""
+    candidates than lanes, asymmetric tables; local alignment with a positive gap cost takes the non-saturating form.
+    Random lengths and letters: the exact edges, planted optima and large costs are in tests/test_gpu_chained_tiers.py."""
     rng = random.Random(hash((kind, gaps)) & 0xFFFF)
     asym_map = np.array([rng.randint(0, 31) for _ in range(256)], dtype=np.uint8)
     asym_tab = np.array([[rng.randint(-9, 9) for _ in range(32)] for _ in range(32)], dtype=np.int8)
@@ -646,6 +647,8 @@ def test_systolic_alignment_fuzz(gpu, oracle, kind, gaps):
 
 @pytest.mark.parametrize("costs", [(0, 1, 1, 1), (1, 3, 3, 3), (0, 1, 4, 2), (2, 5, 4, 1)])
 def test_systolic_levenshtein_fuzz(gpu, oracle, costs):
+    """Weighted and codepoint Levenshtein through hip/systolic.hip, random lengths and letters; the exact lane, band, step and
+    chunk edges are in tests/test_gpu_chained_tiers.py."""
     rng = random.Random(hash(costs) & 0xFFFF)
     with forced_tier("systolic"):
         engine = szs.LevenshteinDistances(*costs, capabilities=gpu)
@@ -688,7 +691,9 @@ def test_systolic_long_pairs_pick_the_tier_themselves(gpu, oracle):
 
 def test_myers_chain_fuzz(gpu, oracle):
     """hip/myers_chain.hip: band edges (2048 rows per wavefront), word edges (32 rows per lane), the 8-column steps and
-    128-column hand-over chunks, empties, bytes >= 0x80, ragged batches, symmetric calls, swapped sides."""
+    128-column hand-over chunks, empties, bytes >= 0x80, ragged batches, symmetric calls, swapped sides.  Random lengths and
+    letters: the exact edges and the structured contents (runs of one delta, partial sums of both signs) are in
+    tests/test_gpu_chained_tiers.py."""
     rng = random.Random(2048)
     engine = szs.LevenshteinDistances(capabilities=gpu)
     with forced_tier("chain"):
@@ -710,7 +715,7 @@ def test_myers_chain_shares_one_mask_table_between_candidates(gpu, oracle, waves
     """A workgroup of hip/myers_chain.hip scores 4 / 8 / 16 candidates against ONE query band (one 64 KB match-mask table):
     candidate counts that do not fill the last workgroup, queries of one and of several bands in one batch, symmetric
     calls (wavefronts above the diagonal leave after the table is built), and the launcher's own choice at a size where
-    it picks 16."""
+    it picks 16.  The exact-length grid under 4 and 16 wavefronts is in tests/test_gpu_chained_tiers.py."""
     rng = random.Random(int(waves))
     engine = szs.LevenshteinDistances(capabilities=gpu)
     with forced_tier("chain"), forced_env("SZS_ROCM_CHAIN_WAVES", waves), forced_swap("0"):
