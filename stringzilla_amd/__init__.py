@@ -226,47 +226,147 @@ def _as_strs(collection) -> Strs:
     return collection if isinstance(collection, Strs) else Strs(collection)
 
 
+def _array_facts(array, name):
+    """-> (shape, item size, byte strides, pointer, GPU index or None) of a NumPy array or a torch tensor; ValueError for anything else.
+    The one place that asks "NumPy or torch?": what an argument must look like stays its caller's rule."""
+    if isinstance(array, np.ndarray):
+        return array.shape, array.dtype.itemsize, array.strides, array.ctypes.data, None
+    if type(array).__module__.partition(".")[0] == "torch" and hasattr(array, "data_ptr"):
+        itemsize = array.element_size()
+        return (tuple(array.shape), itemsize, tuple(stride * itemsize for stride in array.stride()), array.data_ptr(),
+                array.device.index if array.is_cuda else None)
+    raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(array).__name__}")
+
+
 def _listed_cells(matrix, name, shape_wanted):
     """A `(rows, k)` matrix of 8-byte cells with contiguous rows, as `rerank` and `fuzzy_find` take them -> (pointer, row stride in
     cells, shape); ValueError otherwise."""
-    import torch
-
-    if isinstance(matrix, np.ndarray):
-        shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
-        pointer, whole = matrix.ctypes.data, all(s % 8 == 0 for s in matrix.strides)
-    elif type(matrix).__module__.partition(".")[0] == "torch" and hasattr(matrix, "data_ptr"):
-        shape, itemsize, strides, pointer, whole = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr(), True
-        if matrix.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
-            torch.cuda.current_stream(matrix.device).synchronize()
-    else:
-        raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(matrix).__name__}")
-    if len(shape) != 2 or shape[1] < 1 or (shape_wanted is not None and shape != shape_wanted) or itemsize != 8 or not whole or (
-            shape[1] > 1 and strides[1] != 1) or (shape[0] > 1 and strides[0] < shape[1]):
+    shape, itemsize, strides, pointer, _ = _array_facts(matrix, name)
+    if len(shape) != 2 or shape[1] < 1 or (shape_wanted is not None and shape != shape_wanted) or itemsize != 8 or any(
+            stride % 8 for stride in strides) or (shape[1] > 1 and strides[1] != 8) or (shape[0] > 1 and strides[0] < shape[1] * 8):
         raise ValueError(f"`{name}` must be a (rows, k) matrix of 8-byte cells with contiguous rows, k at least 1")
-    return pointer, strides[0] if shape[0] > 1 else shape[1], shape
+    return pointer, strides[0] // 8 if shape[0] > 1 else shape[1], shape
 
 
-def _label_cells(out, rows, gpu_device):
-    """The `out` of a `clusters` call - a contiguous vector of `rows` 8-byte cells, a NumPy array or a torch tensor on the host or on the
-    call's GPU - or, `out` None, a fresh device vector -> (what holds the labels, pointer); ValueError otherwise."""
+def _cells_of_one_stride(named, shape, stride=None):
+    """`_listed_cells` of every (name, matrix) of `named`, which must share one row stride - `stride`, where one is given ->
+    (pointers, that stride)."""
+    pointers = []
+    for name, matrix in named:
+        pointer, own_stride, _ = _listed_cells(matrix, name, shape)
+        if stride is not None and own_stride != stride:
+            raise ValueError(f"`{name}` must share the row stride of the other matrices of the call")
+        stride = own_stride
+        pointers.append(pointer)
+    return pointers, stride
+
+
+def _vector_cells(array, name, rows):
+    """A contiguous vector of `rows` 8-byte cells -> its pointer; ValueError otherwise."""
+    shape, itemsize, strides, pointer, _ = _array_facts(array, name)
+    if shape != (rows,) or itemsize != 8 or (rows > 1 and strides != (8,)):
+        raise ValueError(f"`{name}` must be a contiguous vector of {rows} 8-byte cells")
+    return pointer
+
+
+def _named_out(out, names):
+    """`out` as ((name, array), ...): a tuple or a list with one array per name of `names`; ValueError otherwise."""
+    if not isinstance(out, (tuple, list)) or len(out) != len(names):
+        raise ValueError(f"`out` must be a tuple ({', '.join(names)})")
+    return tuple(zip(("out " + name for name in names), out))
+
+
+def _top_k_out(out, second, shape):
+    """The `out=(indices, second)` of a `top_k`, `second` may be None -> (indices pointer, second pointer or None, row stride,
+    ((name, array), ...)); ValueError otherwise."""
+    try:
+        named = (("out indices", out[0]), ("out " + second, out[1]))
+    except (TypeError, IndexError, KeyError):
+        raise ValueError(f"`out` must be a pair (indices, {second})") from None
+    if named[0][1] is None:
+        raise ValueError("`out indices` must not be None")
+    pointers, stride = _cells_of_one_stride(named if named[1][1] is not None else named[:1], shape)
+    return pointers[0], pointers[1] if len(pointers) > 1 else None, stride, named
+
+
+def _integer(value, name, low, high=None):
+    """`value` as an `int` within [low, high] (`high` None: no upper end); ValueError for a bool, for anything that is no integer, and
+    outside the range."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < low or (
+            high is not None and int(value) > high):
+        raise ValueError(f"{name} must be an integer within [{low}, {'...' if high is None else high}], got {value!r}")
+    return int(value)
+
+
+def _text_bytes(text):
+    """The `text` of a scan, checked without a GPU: bytes-like -> a NumPy view of its bytes; a contiguous `uint8` vector, NumPy or
+    torch -> itself; ValueError otherwise."""
+    if isinstance(text, (bytes, bytearray, memoryview)):
+        return np.frombuffer(text, dtype=np.uint8)
+    try:
+        shape, _, strides, _, _ = _array_facts(text, "text")
+    except ValueError:
+        raise ValueError(f"`text` must be bytes-like, a NumPy uint8 array or a torch uint8 tensor, got {type(text).__name__}") from None
+    if str(text.dtype) not in ("uint8", "torch.uint8") or len(shape) != 1 or (shape[0] > 1 and strides[0] != 1):
+        raise ValueError("`text` must be a contiguous vector of uint8")
+    return text
+
+
+def _text_on_gpu(text, gpu_device):
+    """What `_text_bytes` returned as a tensor on the call's GPU: a tensor already there goes as it is, host data is uploaded once."""
     import torch
 
-    if out is None:
-        labels = torch.empty(max(rows, 1), dtype=torch.int64, device=torch.device("cuda", gpu_device))
-        return labels, labels.data_ptr()
-    if isinstance(out, np.ndarray):
-        shape, itemsize, unit, pointer = out.shape, out.dtype.itemsize, out.strides == (8,), out.ctypes.data
-    elif type(out).__module__.partition(".")[0] == "torch" and hasattr(out, "data_ptr"):
-        shape, itemsize, unit, pointer = tuple(out.shape), out.element_size(), out.stride() == (1,), out.data_ptr()
-    else:
-        raise ValueError(f"`out` must be a NumPy array or a torch tensor, got {type(out).__name__}")
-    if shape != (rows,) or itemsize != 8 or (rows > 1 and not unit):
-        raise ValueError(f"`out` must be a contiguous vector of {rows} 8-byte cells")
-    if getattr(out, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
-        if out.device.index != gpu_device:
-            raise ValueError(f"`out` is on {out.device}, the call runs on GPU {gpu_device}")
-        torch.cuda.current_stream(out.device).synchronize()  # torch's own stream may still be filling it
-    return out, pointer
+    if isinstance(text, np.ndarray):
+        text = torch.from_numpy(text if text.flags.writeable else np.array(text, copy=True))
+    if not text.is_cuda:
+        where = torch.device("cuda", gpu_device)
+        text = text.to(where)
+        torch.cuda.current_stream(where).synchronize()
+    return text
+
+
+def _where(engine, device):
+    """-> (scope, GPU index) of a call.  The three `__call__` bodies keep their own copy of this and of what follows: they are timed."""
+    scope = device or engine._scope or _get_default_scope()
+    return scope, scope.gpu_device if scope.gpu_device is not None else 0
+
+
+def _same_flavour(queries, candidates):
+    """Both sides must use one tape flavour per call, like the binding's detection order (similarities.c:275-318) -> the pair with
+    one offset width."""
+    if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
+        queries, candidates = (Strs.from_tape(side.data, side.offsets.astype(np.uint64)) for side in (queries, candidates))
+    return queries, candidates
+
+
+def _on_call_gpu(named_arrays, gpu_device):
+    """A device tensor goes to the kernel as a raw pointer: one on another GPU than the call's is refused (ValueError).  Whatever torch
+    still has in flight for one on this GPU (a fill, say) runs on TORCH's stream, the call on the scope's own: the former is drained,
+    once, or a late fill overwrites what the call wrote.  `named_arrays`: (name, array or None) pairs, host arrays among them."""
+    drain = False
+    for name, array in named_arrays:
+        if getattr(array, "is_cuda", False):
+            if array.device.index != gpu_device:
+                raise ValueError(f"`{name}` is on {array.device}, the call runs on GPU {gpu_device}")
+            drain = True
+    if drain:
+        import torch
+
+        torch.cuda.current_stream(gpu_device).synchronize()
+
+
+_ONE_SIDED = object()  # the `candidates` of `_tape_call` for an entry that takes one tape
+
+
+def _tape_call(entry, scope, handle, queries, candidates, gpu_device, *arguments):
+    """Calls `entry`'s `_u32tape` or `_u64tape` form - by the offsets of `queries`, which `candidates` (None: NULL) share - with
+    `arguments` behind the tapes, and raises what it reports."""
+    call = getattr(lib, entry + ("_u64tape" if queries.wide_offsets else "_u32tape"))
+    tapes = [ctypes.byref(queries._tape(gpu_device))]
+    if candidates is not _ONE_SIDED:
+        tapes.append(None if candidates is None else ctypes.byref(candidates._tape(gpu_device)))
+    error = ctypes.c_char_p()
+    _abi.check(call(handle, scope.handle, *tapes, *arguments, ctypes.byref(error)), error)
 
 
 class _Engine:
@@ -347,50 +447,19 @@ class _Engine:
         candidates ends in index 2**64 - 1 and score 0."""
         import torch
 
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
-            raise ValueError(f"k must be an integer within [1, 1024], got {k!r}")
-        k = int(k)
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        k = _integer(k, "k", 1, 1024)
         queries = _as_strs(queries)
         candidates = None if candidates is None else _as_strs(candidates)
-        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
-            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
-            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
-        rows = len(queries)
-
-        def cells_of(matrix, name):  # -> (pointer, row stride in cells)
-            if matrix is None:
-                return None, None
-            if isinstance(matrix, np.ndarray):
-                shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
-                pointer = matrix.ctypes.data
-            else:
-                shape, itemsize, strides, pointer = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr()
-                if matrix.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
-                    torch.cuda.current_stream(matrix.device).synchronize()
-            if shape != (rows, k) or itemsize != 8 or (k > 1 and strides[1] != 1):
-                raise ValueError(f"`out` {name} must be a (rows, k) matrix of 8-byte cells with contiguous rows")
-            return pointer, strides[0] if rows > 1 else k
-
+        rows, named = len(queries), ()
+        if out is not None:
+            indices_pointer, scores_pointer, stride, named = _top_k_out(out, "scores", (rows, k))
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu(named, gpu_device)
+        queries, candidates = _same_flavour(queries, candidates)
         if out is None:
             both = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
             indices_pointer, scores_pointer, stride = both[0].data_ptr(), both[1].data_ptr(), k
-        else:
-            indices_pointer, stride = cells_of(out[0], "indices")
-            scores_pointer, scores_stride = cells_of(out[1], "scores")
-            if indices_pointer is None:
-                raise ValueError("`out` indices must not be None")
-            if scores_pointer is not None and scores_stride != stride:
-                raise ValueError("`out` indices and scores must share one row stride")
-
-        error = ctypes.c_char_p()
-        call = lib.szs_rocm_top_k_u64tape if queries.wide_offsets else lib.szs_rocm_top_k_u32tape
-        q_tape = queries._tape(gpu_device)
-        c_tape = None if candidates is None else candidates._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape), k,
-                      indices_pointer, scores_pointer, stride, ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call("szs_rocm_top_k", scope, self.handle, queries, candidates, gpu_device, k, indices_pointer, scores_pointer, stride)
         if out is not None:
             return out
         host = both[:, :rows].cpu().numpy()
@@ -411,31 +480,17 @@ class _Engine:
         if rows != len(queries):
             raise ValueError(f"`indices` must have one row per query: {rows} rows, {len(queries)} queries")
         if out is not None:
-            scores_pointer, scores_stride, _ = _listed_cells(out, "out", (rows, k))
-            if scores_stride != stride:
-                raise ValueError("`out` and `indices` must share one row stride")
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for matrix, name in ((indices, "indices"), (out, "out")):  # a device tensor goes to the kernel as a raw pointer
-            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:
-                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
-        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
-            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
-            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+            (scores_pointer,), _ = _cells_of_one_stride((("out", out),), (rows, k), stride)
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("indices", indices), ("out", out)), gpu_device)
+        queries, candidates = _same_flavour(queries, candidates)
         if out is None:
             if stride == k:
                 results = torch.empty((max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
             else:  # the scores share the stride of the indices: a host matrix as wide as theirs
                 results = np.zeros((max(rows, 1), stride), dtype=np.int64)
             scores_pointer = results.data_ptr() if stride == k else results.ctypes.data
-
-        error = ctypes.c_char_p()
-        call = lib.szs_rocm_rerank_u64tape if queries.wide_offsets else lib.szs_rocm_rerank_u32tape
-        q_tape = queries._tape(gpu_device)
-        c_tape = None if candidates is None else candidates._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
-                      indices_pointer, k, scores_pointer, stride, ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call("szs_rocm_rerank", scope, self.handle, queries, candidates, gpu_device, indices_pointer, k, scores_pointer, stride)
         if out is not None:
             return out
         host = results[:rows].cpu().numpy() if stride == k else results[:rows, :k]
@@ -453,11 +508,10 @@ class _Engine:
         is the shortest best match that ends at `ends[q, r]` - and `out` is a triple in that order."""
         import torch
 
-        names = ("out distances", "out starts", "out ends") if starts else ("out distances", "out ends")
-
+        names = ("distances", "starts", "ends") if starts else ("distances", "ends")
         queries = _as_strs(queries)
         candidates = None if candidates is None else _as_strs(candidates)
-        rows = len(queries)
+        rows, named = len(queries), ()
         if indices is None:
             if candidates is None or len(candidates) < 1:
                 raise ValueError("`indices` None needs at least one candidate; `candidates` None needs `indices`")
@@ -467,24 +521,11 @@ class _Engine:
             if index_rows != rows:
                 raise ValueError(f"`indices` must have one row per query: {index_rows} rows, {rows} queries")
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != len(names):
-                raise ValueError("`out` must be a triple (distances, starts, ends)" if starts else "`out` must be a pair (distances, ends)")
-            pointers = []
-            for matrix, name in zip(out, names):
-                pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
-                if stride is not None and own_stride != stride:
-                    raise ValueError("`out` and `indices` must share one row stride")
-                stride = own_stride
-                pointers.append(pointer)
-            output_pointers = pointers
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for matrix, name in ((indices, "indices"),) + (tuple(zip(out, names)) if out is not None else ()):
-            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
-                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
-        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
-            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
-            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+            named = _named_out(out, names)
+            output_pointers, stride = _cells_of_one_stride(named, (rows, k), stride)
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("indices", indices),) + named, gpu_device)
+        queries, candidates = _same_flavour(queries, candidates)
         if out is None:
             if stride is None or stride == k:
                 stride = k
@@ -493,17 +534,8 @@ class _Engine:
             else:  # the outputs share the stride of the indices: host matrices as wide as theirs
                 results = np.zeros((len(names), max(rows, 1), stride), dtype=np.int64)
                 output_pointers = [matrix.ctypes.data for matrix in results]
-
-        error = ctypes.c_char_p()
-        if starts:
-            call = lib.szs_rocm_fuzzy_find_spans_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_find_spans_u32tape
-        else:
-            call = lib.szs_rocm_fuzzy_find_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_find_u32tape
-        q_tape = queries._tape(gpu_device)
-        c_tape = None if candidates is None else candidates._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
-                      indices_pointer, k, *output_pointers, stride, ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call("szs_rocm_fuzzy_find_spans" if starts else "szs_rocm_fuzzy_find", scope, self.handle, queries, candidates, gpu_device,
+                   indices_pointer, k, *output_pointers, stride)
         if out is not None:
             return out
         host = results[:, :rows].cpu().numpy() if isinstance(results, torch.Tensor) else results[:, :rows, :k]
@@ -547,32 +579,18 @@ class _Engine:
                 raise ValueError("`indices`, `starts` and `ends` must share one row stride")
             stride, k = own_stride, shape[1]
             input_pointers.append(pointer)
-        if capacity is not None and (isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or capacity < 0):
-            raise ValueError(f"capacity must be a non-negative integer, got {capacity!r}")
+        capacity = None if capacity is None else _integer(capacity, "capacity", 0)
+        named = ()
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 3:
-                raise ValueError("`out` must be a triple (distances, lengths, ops)")
-            output_pointers = []
-            for matrix, name in zip(out[:2], ("out distances", "out lengths")):
-                pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
-                if stride is not None and own_stride != stride:
-                    raise ValueError("`out` and `indices` must share one row stride")
-                stride = own_stride
-                output_pointers.append(pointer)
+            named = _named_out(out, ("distances", "lengths", "ops"))
+            output_pointers, stride = _cells_of_one_stride(named[:2], (rows, k), stride)
             ops = out[2]
             if ops is None:
                 if capacity:
                     raise ValueError("`out` ops must not be None when the capacity is not zero")
                 capacity, ops_pointer = 0, None
             else:
-                if isinstance(ops, np.ndarray):
-                    shape, itemsize, strides, ops_pointer = ops.shape, ops.dtype.itemsize, ops.strides, ops.ctypes.data
-                elif type(ops).__module__.partition(".")[0] == "torch" and hasattr(ops, "data_ptr"):
-                    shape, itemsize, strides, ops_pointer = tuple(ops.shape), ops.element_size(), tuple(ops.stride()), ops.data_ptr()
-                    if ops.is_cuda:  # torch's own stream may still be filling it; the call runs on the scope's
-                        torch.cuda.current_stream(ops.device).synchronize()
-                else:
-                    raise ValueError(f"`out` ops must be a NumPy array or a torch tensor, got {type(ops).__name__}")
+                shape, itemsize, strides, ops_pointer, _ = _array_facts(ops, "out ops")  # (bytes: the strides count them)
                 if capacity is None and len(shape) == 3:
                     capacity = shape[2]
                 if len(shape) != 3 or shape != (rows, k, capacity) or itemsize != 1 or capacity < 1 or (
@@ -583,17 +601,9 @@ class _Engine:
             pool = queries if candidates is None else candidates
             longest = lambda strs: int(np.diff(strs.offsets.astype(np.int64)).max()) if len(strs) else 0  # noqa: E731
             capacity = longest(queries) + min(512, longest(pool))
-        capacity = int(capacity)
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        named = (("indices", indices), ("starts", starts), ("ends", ends)) + (tuple(zip(("out distances", "out lengths", "out ops"), out))
-                                                                               if out is not None else ())
-        for name, matrix in named:
-            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
-                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
-        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
-            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
-            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("indices", indices), ("starts", starts), ("ends", ends)) + named, gpu_device)
+        queries, candidates = _same_flavour(queries, candidates)
         if out is None:
             if stride is None or stride == k:
                 stride = k
@@ -604,15 +614,8 @@ class _Engine:
                 cells = np.zeros((2, max(rows, 1), stride), dtype=np.int64)
                 scripts = np.zeros((max(rows, 1), stride, capacity), dtype=np.uint8)
                 output_pointers, ops_pointer = [matrix.ctypes.data for matrix in cells], scripts.ctypes.data if capacity else None
-
-        error = ctypes.c_char_p()
-        call = lib.szs_rocm_alignments_u64tape if queries.wide_offsets else lib.szs_rocm_alignments_u32tape
-        q_tape = queries._tape(gpu_device)
-        c_tape = None if candidates is None else candidates._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape),
-                      input_pointers[0], k, input_pointers[1], input_pointers[2], *output_pointers, ops_pointer, capacity, stride,
-                      ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call("szs_rocm_alignments", scope, self.handle, queries, candidates, gpu_device, input_pointers[0], k, input_pointers[1],
+                   input_pointers[2], *output_pointers, ops_pointer, capacity, stride)
         if out is not None:
             return out
         if isinstance(cells, torch.Tensor):
@@ -631,44 +634,23 @@ class _Engine:
         order, of one row stride, filled and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes."""
         import torch
 
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
-            raise ValueError(f"k must be an integer within [1, 1024], got {k!r}")
-        k = int(k)
-        names = ("out indices", "out distances", "out starts", "out ends") if starts else ("out indices", "out distances", "out ends")
+        k = _integer(k, "k", 1, 1024)
+        names = ("indices", "distances", "starts", "ends") if starts else ("indices", "distances", "ends")
         queries = _as_strs(queries)
         candidates = None if candidates is None else _as_strs(candidates)
-        rows = len(queries)
+        rows, named = len(queries), ()
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != len(names):
-                raise ValueError(f"`out` must be a tuple of {len(names)} matrices: {', '.join(name[4:] for name in names)}")
-            pointers, stride = [], None
-            for matrix, name in zip(out, names):
-                pointer, own_stride, _ = _listed_cells(matrix, name, (rows, k))
-                if stride is not None and own_stride != stride:
-                    raise ValueError("the matrices of `out` must share one row stride")
-                stride = own_stride
-                pointers.append(pointer)
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for matrix, name in (tuple(zip(out, names)) if out is not None else ()):
-            if getattr(matrix, "is_cuda", False) and matrix.device.index != gpu_device:  # a device tensor goes to the kernel as a raw pointer
-                raise ValueError(f"`{name}` is on {matrix.device}, the call runs on GPU {gpu_device}")
-        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
-            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
-            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+            named = _named_out(out, names)
+            pointers, stride = _cells_of_one_stride(named, (rows, k))
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu(named, gpu_device)
+        queries, candidates = _same_flavour(queries, candidates)
         if out is None:
             results = torch.empty((len(names), max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
             pointers, stride = [matrix.data_ptr() for matrix in results], k
-        indices_pointer, distances_pointer, ends_pointer = pointers[0], pointers[1], pointers[-1]
-        starts_pointer = pointers[2] if starts else None
-
-        error = ctypes.c_char_p()
-        call = lib.szs_rocm_fuzzy_search_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_search_u32tape
-        q_tape = queries._tape(gpu_device)
-        c_tape = None if candidates is None else candidates._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape), k,
-                      indices_pointer, distances_pointer, starts_pointer, ends_pointer, stride, ctypes.byref(error))
-        _abi.check(status, error)
+        if not starts:
+            pointers = pointers[:2] + [None] + pointers[2:]  # (indices, distances, no starts, ends)
+        _tape_call("szs_rocm_fuzzy_search", scope, self.handle, queries, candidates, gpu_device, k, *pointers, stride)
         if out is not None:
             return out
         return tuple(matrix.view(np.uint64) for matrix in results[:, :rows].cpu().numpy())
@@ -683,9 +665,8 @@ class _Engine:
         excluded.  `limit=0` counts only: the matrices have shape `(len(queries), 0)`.  `out`: a triple `(counts, indices, scores)`
         of NumPy arrays or torch tensors of 8-byte cells - a contiguous vector and two matrices with contiguous rows of one row
         stride - filled and returned; `scores` may be None, and with `limit=0` so may `indices`.  `limit` at most 65,536."""
-        if isinstance(bound, (bool, np.bool_)) or not isinstance(bound, (int, np.integer)) or not -2**63 <= int(bound) < 2**63:
-            raise ValueError(f"bound must be an integer of 64 signed bits, got {bound!r}")
-        return self._bounded_rows("szs_rocm_within", ("indices", "scores"), ("scores",), queries, candidates, int(bound), limit, device, out)
+        bound = _integer(bound, "bound", -2**63, 2**63 - 1)
+        return self._bounded_rows("szs_rocm_within", ("indices", "scores"), ("scores",), queries, candidates, bound, limit, device, out)
 
     def fuzzy_search_within(self, queries, candidates=None, max_distance=None, limit=64, starts=False, device: Optional[DeviceScope] = None,
                             out=None):
@@ -698,10 +679,9 @@ class _Engine:
         behind hold `(2**64 - 1, 0, 0, 0)`.  A query of no bytes hits every candidate.  `candidates` None: self-search, the own index
         excluded.  `limit=0` counts only.  `out`: a tuple in the order returned, as `within` takes it.  Unit-cost byte Levenshtein
         engines only, queries of at most 256 bytes, `limit` at most 65,536."""
-        if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, np.integer)) or not 0 <= int(max_distance) < 2**64:
-            raise ValueError(f"max_distance must be a non-negative integer below 2**64, got {max_distance!r}")
+        max_distance = _integer(max_distance, "max_distance", 0, 2**64 - 1)
         names = ("indices", "distances", "starts", "ends") if starts else ("indices", "distances", "ends")
-        return self._bounded_rows("szs_rocm_fuzzy_search_within", names, (), queries, candidates, int(max_distance), limit, device, out)
+        return self._bounded_rows("szs_rocm_fuzzy_search_within", names, (), queries, candidates, max_distance, limit, device, out)
 
     def clusters(self, strings, bound, device: Optional[DeviceScope] = None, out=None):
         """The connected components of the graph "i ~ j iff the pair is a `within` hit" (`szs_rocm_clusters_*`): returns
@@ -711,18 +691,19 @@ class _Engine:
         component of `i`, so `labels[labels[i]] == labels[i]` and a string with no neighbour labels itself; `count` is the number of
         components.  Nothing truncates - there is no `limit` - and no knob or tile size changes a byte.  `out`: a contiguous NumPy
         vector or torch tensor of `len(strings)` 8-byte cells, host or device, filled and returned in place of `labels`."""
-        if isinstance(bound, (bool, np.bool_)) or not isinstance(bound, (int, np.integer)) or not -2**63 <= int(bound) < 2**63:
-            raise ValueError(f"bound must be an integer of 64 signed bits, got {bound!r}")
+        import torch
+
+        bound = _integer(bound, "bound", -2**63, 2**63 - 1)
         strings = _as_strs(strings)
         rows = len(strings)
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        labels, pointer = _label_cells(out, rows, gpu_device)
-        error, count = ctypes.c_char_p(), ctypes.c_size_t(0)
-        call = lib.szs_rocm_clusters_u64tape if strings.wide_offsets else lib.szs_rocm_clusters_u32tape
-        tape = strings._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(tape), int(bound), pointer, ctypes.byref(count), ctypes.byref(error))
-        _abi.check(status, error)
+        pointer = None if out is None else _vector_cells(out, "out", rows)
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("out", out),), gpu_device)
+        if out is None:
+            labels = torch.empty(max(rows, 1), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+            pointer = labels.data_ptr()
+        count = ctypes.c_size_t(0)
+        _tape_call("szs_rocm_clusters", scope, self.handle, strings, _ONE_SIDED, gpu_device, bound, pointer, ctypes.byref(count))
         return (labels[:rows].cpu().numpy().view(np.uint64) if out is None else out), int(count.value)
 
     def _bounded_rows(self, entry, names, optional, queries, candidates, bound, limit, device, out):
@@ -730,50 +711,28 @@ class _Engine:
         row behind `entry`'s tape forms (a missing `starts` goes as NULL).  `optional`: the matrices `out` may leave None."""
         import torch
 
-        if isinstance(limit, (bool, np.bool_)) or not isinstance(limit, (int, np.integer)) or not 0 <= int(limit) <= 65536:
-            raise ValueError(f"limit must be an integer within [0, 65536], got {limit!r}")
-        limit = int(limit)
+        limit = _integer(limit, "limit", 0, 65536)
         queries = _as_strs(queries)
         candidates = None if candidates is None else _as_strs(candidates)
-        rows = len(queries)
+        rows, named = len(queries), ()
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 1 + len(names):
-                raise ValueError(f"`out` must be a tuple (counts, {', '.join(names)})")
-            counts = out[0]
-            if isinstance(counts, np.ndarray):
-                shape, itemsize, unit, counts_pointer = counts.shape, counts.dtype.itemsize, counts.strides == (8,), counts.ctypes.data
-            elif type(counts).__module__.partition(".")[0] == "torch" and hasattr(counts, "data_ptr"):
-                shape, itemsize, unit, counts_pointer = tuple(counts.shape), counts.element_size(), counts.stride() == (1,), counts.data_ptr()
-            else:
-                raise ValueError(f"`out counts` must be a NumPy array or a torch tensor, got {type(counts).__name__}")
-            if shape != (rows,) or itemsize != 8 or (rows > 1 and not unit):
-                raise ValueError(f"`out counts` must be a contiguous vector of {rows} 8-byte cells")
+            named = _named_out(out, ("counts",) + names)
+            counts_pointer = _vector_cells(out[0], "out counts", rows)
             pointers, stride = [], None
-            for matrix, name in zip(out[1:], names):
-                if matrix is None and (name in optional or not limit):
+            for name, matrix in named[1:]:
+                if matrix is None and (name[4:] in optional or not limit):
                     pointers.append(None)
-                    continue
-                if not limit:  # never looked at: only the shape is checked
+                elif not limit:  # never looked at: only the shape is checked
                     if tuple(getattr(matrix, "shape", ())) != (rows, 0):
-                        raise ValueError(f"`out {name}` must be None or of shape ({rows}, 0) with limit 0")
+                        raise ValueError(f"`{name}` must be None or of shape ({rows}, 0) with limit 0")
                     pointers.append(None)
-                    continue
-                pointer, own_stride, _ = _listed_cells(matrix, "out " + name, (rows, limit))
-                if stride is not None and own_stride != stride:
-                    raise ValueError("the matrices of `out` must share one row stride")
-                stride = own_stride
-                pointers.append(pointer)
+                else:
+                    (pointer,), stride = _cells_of_one_stride(((name, matrix),), (rows, limit), stride)
+                    pointers.append(pointer)
             stride = limit if stride is None else stride
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for array, name in (tuple(zip(out, ("counts",) + names)) if out is not None else ()):
-            if getattr(array, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
-                if array.device.index != gpu_device:
-                    raise ValueError(f"`out {name}` is on {array.device}, the call runs on GPU {gpu_device}")
-                torch.cuda.current_stream(array.device).synchronize()  # torch's own stream may still be filling it
-        if candidates is not None and queries.wide_offsets != candidates.wide_offsets:
-            queries = Strs.from_tape(queries.data, queries.offsets.astype(np.uint64))
-            candidates = Strs.from_tape(candidates.data, candidates.offsets.astype(np.uint64))
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu(named, gpu_device)
+        queries, candidates = _same_flavour(queries, candidates)
         if out is None:
             where = torch.device("cuda", gpu_device)
             results = (torch.empty(max(rows, 1), dtype=torch.int64, device=where),
@@ -782,14 +741,7 @@ class _Engine:
             pointers = [matrix.data_ptr() if limit else None for matrix in results[1]]
         if entry == "szs_rocm_fuzzy_search_within" and "starts" not in names:
             pointers = pointers[:2] + [None] + pointers[2:]  # (indices, distances, no starts, ends)
-
-        error = ctypes.c_char_p()
-        call = getattr(lib, entry + ("_u64tape" if queries.wide_offsets else "_u32tape"))
-        q_tape = queries._tape(gpu_device)
-        c_tape = None if candidates is None else candidates._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), None if c_tape is None else ctypes.byref(c_tape), bound, limit,
-                      counts_pointer, *pointers, stride, ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call(entry, scope, self.handle, queries, candidates, gpu_device, bound, limit, counts_pointer, *pointers, stride)
         if out is not None:
             return out
         counts, matrices = results[0][:rows].cpu().numpy().view(np.uint64), results[1][:, :rows].cpu().numpy()
@@ -805,60 +757,21 @@ class _Engine:
         and returned.  Unit-cost byte Levenshtein engines only, queries of at most 256 bytes, a text below 4 GiB."""
         import torch
 
-        names = ("out distances", "out starts", "out ends") if starts else ("out distances", "out ends")
+        names = ("distances", "starts", "ends") if starts else ("distances", "ends")
         queries = _as_strs(queries)
-        rows = len(queries)
-        is_tensor = type(text).__module__.partition(".")[0] == "torch" and hasattr(text, "data_ptr")
-        if is_tensor:
-            if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
-                raise ValueError("`text` must be a contiguous vector of uint8")
-        elif isinstance(text, np.ndarray):
-            if text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
-                raise ValueError("`text` must be a contiguous vector of uint8")
-        elif isinstance(text, (bytes, bytearray, memoryview)):
-            text = np.frombuffer(text, dtype=np.uint8)
-        else:
-            raise ValueError(f"`text` must be bytes-like, a NumPy uint8 array or a torch uint8 tensor, got {type(text).__name__}")
+        rows, named = len(queries), ()
+        text = _text_bytes(text)
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != len(names):
-                raise ValueError("`out` must be a triple (distances, starts, ends)" if starts else "`out` must be a pair (distances, ends)")
-            pointers = []
-            for vector, name in zip(out, names):
-                if isinstance(vector, np.ndarray):
-                    shape, itemsize, unit, pointer = vector.shape, vector.dtype.itemsize, vector.strides == (8,), vector.ctypes.data
-                elif type(vector).__module__.partition(".")[0] == "torch" and hasattr(vector, "data_ptr"):
-                    shape, itemsize, unit, pointer = tuple(vector.shape), vector.element_size(), vector.stride() == (1,), vector.data_ptr()
-                else:
-                    raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(vector).__name__}")
-                if shape != (rows,) or itemsize != 8 or (rows > 1 and not unit):
-                    raise ValueError(f"`{name}` must be a contiguous vector of {rows} 8-byte cells")
-                pointers.append(pointer)
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for vector, name in ((text, "text"),) + (tuple(zip(out, names)) if out is not None else ()):
-            if getattr(vector, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
-                if vector.device.index != gpu_device:
-                    raise ValueError(f"`{name}` is on {vector.device}, the call runs on GPU {gpu_device}")
-                torch.cuda.current_stream(vector.device).synchronize()  # torch's own stream may still be filling it
-        where = torch.device("cuda", gpu_device)
-        if not is_tensor:
-            text = torch.from_numpy(np.array(text, copy=True) if not text.flags.writeable else text)
-        if not text.is_cuda:  # host data: uploaded once
-            text = text.to(where)
-            torch.cuda.current_stream(where).synchronize()
+            named = _named_out(out, names)
+            pointers = [_vector_cells(vector, name, rows) for name, vector in named]
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("text", text),) + named, gpu_device)
+        text = _text_on_gpu(text, gpu_device)
         if out is None:
-            results = torch.empty((len(names), max(rows, 1)), dtype=torch.int64, device=where)
+            results = torch.empty((len(names), max(rows, 1)), dtype=torch.int64, device=torch.device("cuda", gpu_device))
             pointers = [vector.data_ptr() for vector in results]
-
-        error = ctypes.c_char_p()
-        if starts:
-            call = lib.szs_rocm_fuzzy_scan_spans_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_scan_spans_u32tape
-        else:
-            call = lib.szs_rocm_fuzzy_scan_u64tape if queries.wide_offsets else lib.szs_rocm_fuzzy_scan_u32tape
-        q_tape = queries._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), text.data_ptr() if text.numel() else None, text.numel(), *pointers,
-                      ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call("szs_rocm_fuzzy_scan_spans" if starts else "szs_rocm_fuzzy_scan", scope, self.handle, queries, _ONE_SIDED, gpu_device,
+                   text.data_ptr() if text.numel() else None, text.numel(), *pointers)
         if out is not None:
             return out
         return tuple(vector.view(np.uint64) for vector in results[:, :rows].cpu().numpy())
@@ -894,65 +807,31 @@ class _Engine:
         `len(names) - 1` matrices of `limit` slots a row behind `entry`'s tape forms (a missing `starts` goes as NULL)."""
         import torch
 
-        for value, name in ((max_distance, "max_distance"), (limit, "limit")):
-            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < 2**64:
-                raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
-        max_distance, limit = int(max_distance), int(limit)
-        if limit > 2**24:
-            raise ValueError(f"limit must be at most 2**24, got {limit}")
+        max_distance, limit = _integer(max_distance, "max_distance", 0, 2**64 - 1), _integer(limit, "limit", 0, 2**24)
         queries = _as_strs(queries)
-        rows = len(queries)
-        is_tensor = type(text).__module__.partition(".")[0] == "torch" and hasattr(text, "data_ptr")
-        if is_tensor:
-            if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
-                raise ValueError("`text` must be a contiguous vector of uint8")
-        elif isinstance(text, np.ndarray):
-            if text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
-                raise ValueError("`text` must be a contiguous vector of uint8")
-        elif isinstance(text, (bytes, bytearray, memoryview)):
-            text = np.frombuffer(text, dtype=np.uint8)
-        else:
-            raise ValueError(f"`text` must be bytes-like, a NumPy uint8 array or a torch uint8 tensor, got {type(text).__name__}")
+        rows, named = len(queries), ()
+        text = _text_bytes(text)
         if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != len(names):
-                raise ValueError(f"`out` must be a tuple ({', '.join(names)})")
-            pointers = []
-            for array, name, wanted in zip(out, names, ((rows,),) + ((rows, limit),) * (len(names) - 1)):
-                if isinstance(array, np.ndarray):
-                    shape, itemsize, dense, pointer = array.shape, array.dtype.itemsize, array.flags.c_contiguous, array.ctypes.data
-                elif type(array).__module__.partition(".")[0] == "torch" and hasattr(array, "data_ptr"):
-                    shape, itemsize, dense, pointer = tuple(array.shape), array.element_size(), array.is_contiguous(), array.data_ptr()
-                else:
-                    raise ValueError(f"`out {name}` must be a NumPy array or a torch tensor, got {type(array).__name__}")
-                if shape != wanted or itemsize != 8 or not dense:
-                    raise ValueError(f"`out {name}` must be a contiguous array of shape {wanted} of 8-byte cells")
-                pointers.append(pointer if len(wanted) == 1 or limit else None)  # limit 0: the matrices are never looked at
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
-        for array, name in ((text, "text"),) + (tuple(zip(out, ("out " + name for name in names))) if out is not None else ()):
-            if getattr(array, "is_cuda", False):  # a device tensor goes to the kernel as a raw pointer
-                if array.device.index != gpu_device:
-                    raise ValueError(f"`{name}` is on {array.device}, the call runs on GPU {gpu_device}")
-                torch.cuda.current_stream(array.device).synchronize()  # torch's own stream may still be filling it
-        where = torch.device("cuda", gpu_device)
-        if not is_tensor:
-            text = torch.from_numpy(np.array(text, copy=True) if not text.flags.writeable else text)
-        if not text.is_cuda:  # host data: uploaded once
-            text = text.to(where)
-            torch.cuda.current_stream(where).synchronize()
+            named = _named_out(out, names)
+            pointers = [_vector_cells(out[0], "out counts", rows)]
+            for name, matrix in named[1:]:  # the C entries take no row stride: the matrices are contiguous as a whole
+                shape, itemsize, strides, pointer, _ = _array_facts(matrix, name)
+                dense = 0 in shape or all(extent == 1 or stride == step for extent, stride, step in zip(shape, strides, (limit * 8, 8)))
+                if shape != (rows, limit) or itemsize != 8 or not dense:
+                    raise ValueError(f"`{name}` must be a contiguous array of shape {(rows, limit)} of 8-byte cells")
+                pointers.append(pointer if limit else None)  # limit 0: the matrices are never looked at
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("text", text),) + named, gpu_device)
+        text = _text_on_gpu(text, gpu_device)
         if out is None:
+            where = torch.device("cuda", gpu_device)
             results = (torch.empty(max(rows, 1), dtype=torch.int64, device=where),
                        torch.empty((len(names) - 1, max(rows, 1), limit), dtype=torch.int64, device=where))
             pointers = [results[0].data_ptr()] + [matrix.data_ptr() if limit else None for matrix in results[1]]
-
-        error = ctypes.c_char_p()
-        call = getattr(lib, entry + ("_u64tape" if queries.wide_offsets else "_u32tape"))
         if entry == "szs_rocm_fuzzy_scan_occurrences" and "starts" not in names:
             pointers = pointers[:2] + [None] + pointers[2:]  # (counts, distances, no starts, ends)
-        q_tape = queries._tape(gpu_device)
-        status = call(self.handle, scope.handle, ctypes.byref(q_tape), text.data_ptr() if text.numel() else None, text.numel(), max_distance,
-                      limit, *pointers, ctypes.byref(error))
-        _abi.check(status, error)
+        _tape_call(entry, scope, self.handle, queries, _ONE_SIDED, gpu_device, text.data_ptr() if text.numel() else None, text.numel(),
+                   max_distance, limit, *pointers)
         if out is not None:
             return out
         counts, matrices = results[0][:rows].cpu().numpy().view(np.uint64), results[1][:, :rows].cpu().numpy().view(np.uint64)
@@ -1077,43 +956,23 @@ class Fingerprints:
         return both[0], both[1]
 
     def _hashes(self, matrix, name):
-        """-> (pointer, row stride in bytes, rows, GPU index or None) of an `(n, ndim)` matrix of 32-bit hashes with contiguous
-        rows: a `uint32` NumPy array, or an `int32` / `uint32` torch tensor on the host or on a GPU (passed by pointer)."""
+        """-> (pointer, row stride in bytes, rows, what `_on_call_gpu` looks at) of an `(n, ndim)` matrix of 32-bit hashes with
+        contiguous rows: a `uint32` NumPy array, or an `int32` / `uint32` torch tensor on the host or on a GPU (passed by pointer)."""
         ndim = self.ndim
-        if isinstance(matrix, np.ndarray):
-            if matrix.ndim != 2 or matrix.shape[1] != ndim or matrix.dtype != np.uint32:
-                raise ValueError(f"`{name}` must be an (n, {ndim}) matrix of uint32 hashes")
-            rows = matrix.shape[0]  # (the strides of an empty or one-row matrix say nothing)
-            if rows and (matrix.strides[1] != 4 or (rows > 1 and (matrix.strides[0] < ndim * 4 or matrix.strides[0] % 4))):
-                raise ValueError(f"`{name}` must have contiguous rows")
-            return matrix.ctypes.data if rows else _NO_ROWS.ctypes.data, matrix.strides[0] if rows > 1 else ndim * 4, rows, None
-        if type(matrix).__module__.partition(".")[0] != "torch" or not hasattr(matrix, "data_ptr"):
-            raise ValueError(f"`{name}` must be a NumPy array or a torch tensor, got {type(matrix).__name__}")
-        if matrix.dim() != 2 or matrix.shape[1] != ndim or str(matrix.dtype) not in ("torch.int32", "torch.uint32"):
-            raise ValueError(f"`{name}` must be an (n, {ndim}) matrix of int32 / uint32 hashes")
-        rows = matrix.shape[0]
-        if rows and (matrix.stride(1) != 1 or (rows > 1 and matrix.stride(0) < ndim)):
+        shape, _, strides, pointer, _ = _array_facts(matrix, name)
+        if len(shape) != 2 or shape[1] != ndim or str(matrix.dtype) not in ("uint32", "torch.int32", "torch.uint32"):
+            raise ValueError(f"`{name}` must be an (n, {ndim}) matrix of uint32 (a tensor: int32 / uint32) hashes")
+        rows = shape[0]  # (the strides of an empty or one-row matrix say nothing)
+        if rows and (strides[1] != 4 or (rows > 1 and (strides[0] < ndim * 4 or strides[0] % 4))):
             raise ValueError(f"`{name}` must have contiguous rows")
         if not rows:  # torch gives an empty tensor the pointer 0, and a NULL candidate matrix means self-search to the library
             return _NO_ROWS.ctypes.data, ndim * 4, 0, None
-        return matrix.data_ptr(), (matrix.stride(0) if rows > 1 else ndim) * 4, rows, matrix.device.index if matrix.is_cuda else None
+        return pointer, strides[0] if rows > 1 else ndim * 4, rows, matrix
 
     def _search_inputs(self, query_hashes, candidate_hashes):
         queries = self._hashes(query_hashes, "query_hashes")
         candidates = None if candidate_hashes is None else self._hashes(candidate_hashes, "candidate_hashes")
-        return queries, candidates
-
-    @staticmethod
-    def _drain_torch(gpu_device, *sides):
-        """Whatever torch still has in flight for a GPU tensor runs on TORCH's stream; the search runs on the scope's own.  A tensor
-        on another GPU than the scope's is refused: its pointer means nothing there."""
-        devices = {side[3] for side in sides if side is not None and side[3] is not None}
-        if devices - {gpu_device}:
-            raise ValueError(f"GPU tensors must live on the scope's GPU {gpu_device}, got one on GPU {min(devices - {gpu_device})}")
-        if devices:
-            import torch
-
-            torch.cuda.current_stream(gpu_device).synchronize()
+        return queries, candidates, (("query_hashes", queries[3]), ("candidate_hashes", None if candidates is None else candidates[3]))
 
     def matches(self, query_hashes, candidate_hashes=None, device: Optional[DeviceScope] = None, out=None):
         """Equal dimensions of every (query, candidate) pair of fingerprints (`szs_rocm_fingerprint_matches`): a `(Q, C)` `uint32`
@@ -1122,28 +981,18 @@ class Fingerprints:
         themselves, diagonal included (= `ndim`).  `out`: a `(Q, C)` NumPy array or torch tensor of `int32` / `uint32` cells with
         contiguous rows, filled and returned.  GPU tensors must live on the scope's GPU.  The Jaccard estimate of a pair is
         `matches / ndim`: that division stays the caller's.  Equality is plain: two 0xFFFFFFFF hashes (a text shorter than the window) count as equal."""
-        queries, candidates = self._search_inputs(query_hashes, candidate_hashes)
         import torch
 
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        queries, candidates, named = self._search_inputs(query_hashes, candidate_hashes)
         rows, columns = queries[2], queries[2] if candidates is None else candidates[2]
-        error = "`out` must be a (queries, candidates) matrix of int32 / uint32 cells with contiguous rows"
-        if out is None:
-            out_device = None
-        elif isinstance(out, np.ndarray):
-            if out.shape != (rows, columns) or out.dtype not in (np.uint32, np.int32) or (columns > 1 and out.strides[1] != 4) or out.strides[0] % 4:
-                raise ValueError(error)
-            pointer, stride, out_device = out.ctypes.data, out.strides[0] if rows > 1 else max(columns, 1) * 4, None
-        else:
-            if type(out).__module__.partition(".")[0] != "torch" or not hasattr(out, "data_ptr"):
-                raise ValueError(error)
-            if tuple(out.shape) != (rows, columns) or str(out.dtype) not in ("torch.int32", "torch.uint32") or (
-                    columns > 1 and out.stride(1) != 1):
-                raise ValueError(error)
-            pointer, stride = out.data_ptr(), (out.stride(0) if rows > 1 else max(columns, 1)) * 4
-            out_device = out.device.index if out.is_cuda else None
-        self._drain_torch(gpu_device, queries, candidates, (0, 0, 0, out_device))
+        if out is not None:
+            shape, _, strides, pointer, _ = _array_facts(out, "out")
+            if shape != (rows, columns) or str(out.dtype) not in ("uint32", "int32", "torch.int32", "torch.uint32") or (
+                    columns > 1 and strides[1] != 4) or strides[0] % 4:
+                raise ValueError("`out` must be a (queries, candidates) matrix of int32 / uint32 cells with contiguous rows")
+            stride = strides[0] if rows > 1 else max(columns, 1) * 4
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu(named + (("out", out),), gpu_device)
         if out is None:
             results = torch.empty((max(rows, 1), max(columns, 1)), dtype=torch.int32, device=torch.device("cuda", gpu_device))
             pointer, stride = results.data_ptr(), max(columns, 1) * 4
@@ -1163,39 +1012,16 @@ class Fingerprints:
         index.  `candidate_hashes` None: self-search, each query's own index excluded (identical fingerprints at other indices
         count).  A row with fewer than `k` candidates ends in index 2**64 - 1 and count 0.  The Jaccard estimate of a hit is
         `matches / ndim`: that division stays the caller's."""
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024:
-            raise ValueError(f"k must be an integer within [1, 1024], got {k!r}")
-        k = int(k)
-        queries, candidates = self._search_inputs(query_hashes, candidate_hashes)
         import torch
 
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
+        k = _integer(k, "k", 1, 1024)
+        queries, candidates, named = self._search_inputs(query_hashes, candidate_hashes)
         rows = queries[2]
-        out_devices = []
-
-        def cells_of(matrix, name):  # -> (pointer, row stride in cells)
-            if matrix is None:
-                return None, None
-            if isinstance(matrix, np.ndarray):
-                shape, itemsize, strides = matrix.shape, matrix.dtype.itemsize, tuple(s // 8 for s in matrix.strides)
-                pointer = matrix.ctypes.data
-            else:
-                shape, itemsize, strides, pointer = tuple(matrix.shape), matrix.element_size(), tuple(matrix.stride()), matrix.data_ptr()
-                if matrix.is_cuda:
-                    out_devices.append((0, 0, 0, matrix.device.index))
-            if shape != (rows, k) or itemsize != 8 or (k > 1 and strides[1] != 1):
-                raise ValueError(f"`out` {name} must be a (rows, k) matrix of 8-byte cells with contiguous rows")
-            return pointer, strides[0] if rows > 1 else k
-
         if out is not None:
-            indices_pointer, stride = cells_of(out[0], "indices")
-            matches_pointer, matches_stride = cells_of(out[1], "matches")
-            if indices_pointer is None:
-                raise ValueError("`out` indices must not be None")
-            if matches_pointer is not None and matches_stride != stride:
-                raise ValueError("`out` indices and matches must share one row stride")
-        self._drain_torch(gpu_device, queries, candidates, *out_devices)
+            indices_pointer, matches_pointer, stride, named_out = _top_k_out(out, "matches", (rows, k))
+            named += named_out
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu(named, gpu_device)
         if out is None:
             both = torch.empty((2, max(rows, 1), k), dtype=torch.int64, device=torch.device("cuda", gpu_device))
             indices_pointer, matches_pointer, stride = both[0].data_ptr(), both[1].data_ptr(), k
@@ -1216,16 +1042,19 @@ class Fingerprints:
         smallest row of the component of row `i`, a `uint64` NumPy vector, and the number of components.  `hashes` as `top_k` takes
         them.  `min_matches=0` makes every pair a hit - one cluster; beyond `ndim` none.  `out`: a contiguous NumPy vector or torch
         tensor of 8-byte cells, host or device, filled and returned in place of `labels`."""
-        if isinstance(min_matches, (bool, np.bool_)) or not isinstance(min_matches, (int, np.integer)) or not 0 <= int(min_matches) < 2**64:
-            raise ValueError(f"min_matches must be a non-negative integer below 2**64, got {min_matches!r}")
+        import torch
+
+        min_matches = _integer(min_matches, "min_matches", 0, 2**64 - 1)
         side = self._hashes(hashes, "hashes")
-        scope = device or self._scope or _get_default_scope()
-        gpu_device = scope.gpu_device if scope.gpu_device is not None else 0
         rows = side[2]
-        self._drain_torch(gpu_device, side)
-        labels, pointer = _label_cells(out, rows, gpu_device)
+        pointer = None if out is None else _vector_cells(out, "out", rows)
+        scope, gpu_device = _where(self, device)
+        _on_call_gpu((("hashes", side[3]), ("out", out)), gpu_device)
+        if out is None:
+            labels = torch.empty(max(rows, 1), dtype=torch.int64, device=torch.device("cuda", gpu_device))
+            pointer = labels.data_ptr()
         message, count = ctypes.c_char_p(), ctypes.c_size_t(0)
-        status = lib.szs_rocm_fingerprint_clusters(self.handle, scope.handle, side[0], side[1], rows, int(min_matches), pointer,
+        status = lib.szs_rocm_fingerprint_clusters(self.handle, scope.handle, side[0], side[1], rows, min_matches, pointer,
                                                    ctypes.byref(count), ctypes.byref(message))
         _abi.check(status, message)
         return (labels[:rows].cpu().numpy().view(np.uint64) if out is None else out), int(count.value)

@@ -13,6 +13,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _no_gpu_engine
+
 ALIGNMENTS_SYMBOLS = ("szs_rocm_alignments", "szs_rocm_alignments_u32tape", "szs_rocm_alignments_u64tape")
 UNTOUCHED = 0x5A5A5A5A5A5A5A5A
 CAPACITY = 8
@@ -83,10 +85,6 @@ def test_dimensions_are_refused(name, k, row_stride):
         status, _ = _call(name, engine, k, row_stride, indices, None, None, *outputs)
         assert _abi.STATUS_NAMES[status] == "unexpected_dimensions"
         assert _untouched(*outputs)
-
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arrays must be refused before either is needed
 
 
 def _cells(shape=(2, 3), dtype=np.uint64):

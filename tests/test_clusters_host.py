@@ -8,6 +8,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _EngineHead, _fake_engine, _no_gpu_engine
+
 import clusters_cases as cases
 
 SYMBOLS = ("szs_rocm_clusters", "szs_rocm_clusters_u32tape", "szs_rocm_clusters_u64tape")
@@ -78,21 +80,6 @@ def test_probe_edges():
 # ---- the refusals, in order, on memory that passes for an engine ---------------------------------------------------------------------
 
 
-class _EngineHead(ctypes.Structure):
-    """The first members of `szs_engine_s` (csrc/host/szs_internal.h)."""
-    _fields_ = [("magic", ctypes.c_uint32), ("family", ctypes.c_int), ("costs", ctypes.c_int8 * 4), ("byte_to_class", ctypes.c_uint8 * 256),
-                ("class_costs", ctypes.c_int8 * 1024), ("is_linear", ctypes.c_int), ("is_unit_cost", ctypes.c_int)]
-
-
-def _fake_engine(family=0):
-    """Memory that passes for an engine up to the point where a GPU would be needed."""
-    blank = ctypes.create_string_buffer(1 << 16)
-    head = _EngineHead.from_buffer(blank)
-    head.magic, head.family, head.is_linear, head.is_unit_cost = 0x535A5345, family, 1, 1
-    head.costs[:] = [0, 1, 1, 1]
-    return blank
-
-
 def _call(name, engine, labels, count_word, count=2, strings=True):
     """One C call over `count` strings; `labels` None for NULL; -> (status name, message)."""
     data = np.frombuffer(b"abcabd", dtype=np.uint8).copy()
@@ -158,10 +145,6 @@ def test_fingerprint_refusals():
     similarity = _fake_engine()
     assert call(ctypes.addressof(similarity), 16, 2) == "unknown"  # a similarity engine is no fingerprints engine
     assert (labels == UNTOUCHED).all() and (word == UNTOUCHED).all()
-
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arguments must be refused before either is needed
 
 
 @pytest.mark.parametrize("bound", [None, 1.5, True, 2**63, -2**63 - 1, "1"])

@@ -158,9 +158,13 @@ def test_python_matches_rejects_bad_out_before_the_library(flaw):
 
 def test_python_rejects_tensors_of_another_gpu():
     """A pointer into another GPU's memory means nothing on the scope's: refused before torch or the library is asked."""
-    queries, elsewhere = (1, NDIM * 4, 2, 0), (1, NDIM * 4, 2, 1)
+    import types
+
+    def tensor_on(index):  # what the check looks at of a device tensor
+        return types.SimpleNamespace(is_cuda=True, device=types.SimpleNamespace(index=index))
+
     with pytest.raises(ValueError):
-        szs.Fingerprints._drain_torch(0, queries, elsewhere)
+        szs._on_call_gpu((("query_hashes", tensor_on(0)), ("candidate_hashes", tensor_on(1))), 0)
     with pytest.raises(ValueError):
-        szs.Fingerprints._drain_torch(1, queries, None)
-    szs.Fingerprints._drain_torch(0, (1, NDIM * 4, 2, None), None)  # host memory on both sides: nothing to check or drain
+        szs._on_call_gpu((("query_hashes", tensor_on(0)), ("candidate_hashes", None)), 1)
+    szs._on_call_gpu((("query_hashes", _hashes()), ("candidate_hashes", None)), 0)  # host memory on both sides: nothing to check or drain

@@ -11,6 +11,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _fake_engine, _no_gpu_engine
+
 PLAIN = ("szs_rocm_fuzzy_scan", "szs_rocm_fuzzy_scan_u32tape", "szs_rocm_fuzzy_scan_u64tape")
 SPANS = ("szs_rocm_fuzzy_scan_spans", "szs_rocm_fuzzy_scan_spans_u32tape", "szs_rocm_fuzzy_scan_spans_u64tape")
 UNTOUCHED = 0x5A5A5A5A5A5A5A5A
@@ -41,21 +43,6 @@ def _call(name, engine, text, text_length, distances, starts, ends, count=2, nul
     outputs = (pointer(distances), pointer(starts), pointer(ends)) if "spans" in name else (pointer(distances), pointer(ends))
     status = getattr(_abi.lib, name)(engine, None, None if null_queries else ctypes.byref(tape), text, text_length, *outputs, ctypes.byref(error))
     return status, error.value
-
-
-class _EngineHead(ctypes.Structure):
-    """The first members of `szs_engine_s` (csrc/host/szs_internal.h), up to the flag the call reads."""
-    _fields_ = [("magic", ctypes.c_uint32), ("family", ctypes.c_int), ("costs", ctypes.c_int8 * 4), ("byte_to_class", ctypes.c_uint8 * 256),
-                ("class_costs", ctypes.c_int8 * 1024), ("is_linear", ctypes.c_int), ("is_unit_cost", ctypes.c_int)]
-
-
-def _fake_engine(family=0, unit_cost=1):
-    """Memory that passes for an engine up to the point where a GPU would be needed: the magic, the family, the unit-cost flag."""
-    blank = ctypes.create_string_buffer(1 << 16)
-    head = _EngineHead.from_buffer(blank)
-    head.magic, head.family, head.is_linear, head.is_unit_cost = 0x535A5345, family, 1, unit_cost
-    head.costs[:] = [0, 1, 1, 1] if unit_cost else [0, 2, 3, 1]
-    return blank
 
 
 def _outputs():
@@ -163,10 +150,6 @@ def test_probe_refusals():
 
 
 # ---- the Python wrapper ------------------------------------------------------------------------------------------------------
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arguments must be refused before either is needed
-
 
 @pytest.mark.parametrize("out", [
     (np.zeros(2, dtype=np.float32),) * 2,

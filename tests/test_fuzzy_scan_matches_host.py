@@ -11,6 +11,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _fake_engine, _no_gpu_engine
+
 NAMES = ("szs_rocm_fuzzy_scan_matches", "szs_rocm_fuzzy_scan_matches_u32tape", "szs_rocm_fuzzy_scan_matches_u64tape")
 UNTOUCHED = 0x5A5A5A5A5A5A5A5A
 LIMIT = 3
@@ -49,21 +51,6 @@ def _call(name, engine, text, text_length, max_distance, limit, counts, distance
     status = getattr(_abi.lib, name)(engine, None, None if null_queries else ctypes.byref(tape), text, text_length, max_distance, limit,
                                      pointer(counts), pointer(distances), pointer(ends), ctypes.byref(error))
     return _abi.STATUS_NAMES[status], error.value
-
-
-class _EngineHead(ctypes.Structure):
-    """The first members of `szs_engine_s` (csrc/host/szs_internal.h), up to the flag the call reads."""
-    _fields_ = [("magic", ctypes.c_uint32), ("family", ctypes.c_int), ("costs", ctypes.c_int8 * 4), ("byte_to_class", ctypes.c_uint8 * 256),
-                ("class_costs", ctypes.c_int8 * 1024), ("is_linear", ctypes.c_int), ("is_unit_cost", ctypes.c_int)]
-
-
-def _fake_engine(family=0, unit_cost=1):
-    """Memory that passes for an engine up to the point where a GPU would be needed: the magic, the family, the unit-cost flag."""
-    blank = ctypes.create_string_buffer(1 << 16)
-    head = _EngineHead.from_buffer(blank)
-    head.magic, head.family, head.is_linear, head.is_unit_cost = 0x535A5345, family, 1, unit_cost
-    head.costs[:] = [0, 1, 1, 1] if unit_cost else [0, 2, 3, 1]
-    return blank
 
 
 def _outputs():
@@ -153,10 +140,6 @@ def test_the_counting_form_takes_null_matrices_and_reaches_the_text_check(name):
 
 
 # ---- the Python wrapper ------------------------------------------------------------------------------------------------------
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arguments must be refused before either is needed
-
 
 def _good():
     return np.zeros(2, dtype=np.uint64), np.zeros((2, LIMIT), dtype=np.uint64), np.zeros((2, LIMIT), dtype=np.uint64)

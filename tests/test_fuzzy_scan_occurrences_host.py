@@ -11,7 +11,8 @@ import pytest
 
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
-from test_fuzzy_scan_matches_host import _fake_engine, _no_gpu_engine
+
+from host_fakes import _fake_engine, _no_gpu_engine
 
 NAMES = ("szs_rocm_fuzzy_scan_occurrences", "szs_rocm_fuzzy_scan_occurrences_u32tape", "szs_rocm_fuzzy_scan_occurrences_u64tape")
 UNTOUCHED = 0x5A5A5A5A5A5A5A5A

@@ -14,6 +14,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _no_gpu_engine
+
 SPANS_SYMBOLS = ("szs_rocm_fuzzy_find_spans", "szs_rocm_fuzzy_find_spans_u32tape", "szs_rocm_fuzzy_find_spans_u64tape")
 UNTOUCHED = 0x5A5A5A5A5A5A5A5A
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,10 +81,6 @@ def test_dimensions_are_refused(name, k, row_stride):
         assert _abi.STATUS_NAMES[status] == "unexpected_dimensions"
         assert _call(name, engine, k, row_stride, indices, distances, None, ends, plain=True)[0] == status
         assert _untouched(distances, starts, ends)
-
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arrays must be refused before either is needed
 
 
 def _triple(matrix):

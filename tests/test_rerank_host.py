@@ -7,6 +7,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _fake_engine, _no_gpu_engine
+
 RERANK_SYMBOLS = ("szs_rocm_rerank", "szs_rocm_rerank_u32tape", "szs_rocm_rerank_u64tape")
 UNTOUCHED = 0x5A5A5A5A5A5A5A5A
 
@@ -32,13 +34,6 @@ def _call(name, engine, k, row_stride, indices, scores, count=2):
     status = getattr(_abi.lib, name)(engine, None, query, query, None if indices is None else indices.ctypes.data, k,
                                      None if scores is None else scores.ctypes.data, row_stride, ctypes.byref(error))
     return status, error.value
-
-
-def _fake_engine():
-    """Memory that passes for a unit-cost Levenshtein engine up to the point where a GPU would be needed: the magic, family 0."""
-    blank = ctypes.create_string_buffer(1 << 16)
-    ctypes.cast(blank, ctypes.POINTER(ctypes.c_uint32))[0] = 0x535A5345
-    return blank
 
 
 @pytest.mark.parametrize("name", RERANK_SYMBOLS)
@@ -86,10 +81,6 @@ def test_rerank_knob_is_known():
         assert _abi._knob_values["rerank"] is None
     finally:
         _abi.tuning_set("rerank", previous)
-
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arrays must be refused before either is needed
 
 
 @pytest.mark.parametrize("indices", [

@@ -9,6 +9,8 @@ import pytest
 import stringzilla_amd as szs
 from stringzilla_amd import _abi
 
+from host_fakes import _fake_engine, _no_gpu_engine
+
 import within_cases as cases
 
 WITHIN_SYMBOLS = ("szs_rocm_within", "szs_rocm_within_u32tape", "szs_rocm_within_u64tape")
@@ -31,21 +33,6 @@ def test_symbols_exported_and_bound():
 
 
 # ---- the refusals, in order, on memory that passes for an engine -------------------------------------------------------------------
-
-
-class _EngineHead(ctypes.Structure):
-    """The first members of `szs_engine_s` (csrc/host/szs_internal.h), up to the flag the calls read."""
-    _fields_ = [("magic", ctypes.c_uint32), ("family", ctypes.c_int), ("costs", ctypes.c_int8 * 4), ("byte_to_class", ctypes.c_uint8 * 256),
-                ("class_costs", ctypes.c_int8 * 1024), ("is_linear", ctypes.c_int), ("is_unit_cost", ctypes.c_int)]
-
-
-def _fake_engine(family=0, unit_cost=1):
-    """Memory that passes for an engine up to the point where a GPU would be needed: the magic, the family, the unit-cost flag."""
-    blank = ctypes.create_string_buffer(1 << 16)
-    head = _EngineHead.from_buffer(blank)
-    head.magic, head.family, head.is_linear, head.is_unit_cost = 0x535A5345, family, 1, unit_cost
-    head.costs[:] = [0, 1, 1, 1] if unit_cost else [0, 2, 3, 1]
-    return blank
 
 
 def _call(name, engine, limit, row_stride, arrays, count=2, queries=True):
@@ -124,10 +111,6 @@ def test_fuzzy_outputs_that_need_another():
     status, message = _call("szs_rocm_fuzzy_search_within_u32tape", ctypes.addressof(engine), 2, 3, [counts, indices, distances, starts, None])
     assert status == "unknown" and b"ends" in message
     assert _intact(arrays)
-
-
-def _no_gpu_engine():
-    return object.__new__(szs.LevenshteinDistances)  # no handle, no GPU: the arguments must be refused before either is needed
 
 
 @pytest.mark.parametrize("arguments", [
